@@ -7,8 +7,17 @@ lr=1e-5 (Stage II = 0.1 x 1e-4), wd=1e-5, train mode with Dropout2d.
 A step = zero_grad -> forward -> fused loss -> backward (+ RCCL bucketed
 all-reduce when N > 1) -> AdamW, inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...       (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, ms_per_step, ...): nothing else runs and no launch hook or tracer is installed.
+``--full`` adds everything else the line has carried: the live per-kernel rooflines (HIP events
+around the launches of the timed steps), the isolated extra step, the standalone loss and HBM
+probes, the PMC figures, the exposed all-reduce time for N > 1 and the CPU baseline
+(``--no-cpu-baseline`` leaves that one out). ``--dump-outputs DIR`` writes what the last timed
+step computed as DIR/<name>.npy (float32 / float64, see dump_outputs); inputs, initial weights
+and dropout seeds are fixed, so two builds can be compared output for output.
 
 With ``--gpus N > 1`` and no torchrun environment (WORLD_SIZE unset), bench.py is
 its own launcher: before anything touches the GPU it starts N child processes of
@@ -598,12 +607,57 @@ def dist_summary(bucketer, device, backend):
                     "GradBucketer.finish() waited for the bucketed all-reduces (per timed step)"}
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each parameter-sized array (8 MiB as float32)
+
+
+def dump_outputs(path: str, model, u: torch.Tensor, loss: torch.Tensor) -> None:
+    """What the last timed step handed its caller, as ``path/<name>.npy``: ``u`` (the probabilities
+    the forward returned, float32, whole), ``loss`` (float64 scalar), and a fixed seeded sample
+    (the same DUMP_SAMPLE arena positions in every run) of the parameters after the AdamW update
+    (``params_sample``) and of the gradients that update consumed (``grads_sample``), float32.
+    At the largest config (1024 x 1024) this is 32 + 8 + 8 MiB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arena = model.arena
+    idx = torch.randperm(arena.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_SAMPLE].sort().values
+    idx = idx.to(arena.device)
+    arrays = {
+        "u": u.detach().float().cpu().numpy(),
+        "loss": np.asarray(loss.detach().double().cpu().numpy(), dtype=np.float64),
+        "params_sample": arena.detach()[idx].cpu().numpy(),
+        "grads_sample": model.grad_arena().detach()[idx].cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def headline(args, world: int, imgs_per_s: float, ms: float, workload: str, final_loss: float) -> dict:
+    """The fields every run prints: the headline figure and what it was measured on."""
+    return {
+        "metric": ("training images/sec (512x512, Stage-II RD+PF loss)" if args.config == "c2"
+                   else f"training images/sec ({H}x{W}, {args.config})"),
+        "value": imgs_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "fp32 (fp16x3 split MFMA, power-of-two block scales; direct + Winograd convs)", "data": "synthetic",
+        "config": {"workload": workload,
+                   "global_batch": B * world, "image_size": [H, W], "parallelism": f"dp{world}"},
+        "roofline": None,
+        "final_loss": final_loss,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline: per-kernel rooflines (launch "
+                         "hooks over the timed steps), the isolated step, loss / HBM probes, PMC figures, "
+                         "exposed all-reduce time (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse "
@@ -647,11 +701,12 @@ def main():
         opt.zero_grad()
         # u = model(x); loss = crit(u, t) with the head and the loss forward in one kernel
         # (UNet.forward_with_loss: pis_head_loss_fwd), as train_epoch runs it
-        _, loss = model.forward_with_loss(x, t, crit)
+        u, loss = model.forward_with_loss(x, t, crit)
         loss.backward()
         opt.step()
-        return loss
+        return u, loss
 
+    u = loss = None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -661,17 +716,19 @@ def main():
     # roofline of the dominant kernel, live over the timed region: HIP events recorded on the
     # launch stream right around each of its launches (pis_set_launch_hook), and around the
     # fused-loss C-ABI calls (host-side enqueue only; the GPU stays the bottleneck)
+    # (--full only: a plain run times the steps with nothing installed)
     from physics_informed_image_segmentation_amd import _hip
     ktimer, ftimer, ltimer = KernelTimer(), KernelTimer("wino_gemm_out"), LossCallTimer()
     htimer = KernelTimer("head_loss_fwd")  # its hook "flop" carries the launch's algorithmic bytes
     dtimers = {k: KernelTimer(k) for k in DIRECT_ROLES}
-    _hip.set_launch_hook(lambda *a: (ktimer(*a), ftimer(*a), htimer(*a), *(tm(*a) for tm in dtimers.values())))
-    _hip.set_tracer(ltimer)
-    if bucketer is not None:
-        bucketer.timing = True
+    if args.full:
+        _hip.set_launch_hook(lambda *a: (ktimer(*a), ftimer(*a), htimer(*a), *(tm(*a) for tm in dtimers.values())))
+        _hip.set_tracer(ltimer)
+        if bucketer is not None:
+            bucketer.timing = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        u, loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -689,6 +746,18 @@ def main():
         dt = max(tt.tolist())
     ms = dt / args.steps * 1e3
     imgs_per_s = world * B * args.steps / dt
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, u, loss)
+    if not args.full:
+        if rank == 0:
+            out = headline(args, world, imgs_per_s, ms, workload, final_loss)
+            if rank_ms is not None:
+                out["ms_per_step_by_rank"] = rank_ms
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     dist_info = None
     if bucketer is not None:
         bucketer.timing = False
@@ -808,15 +877,8 @@ def main():
     hbm = hbm_probe(device)
     if rank == 0:
         flops = conv_flops_per_image(H, W) * B
-        out = {
-            "metric": ("training images/sec (512x512, Stage-II RD+PF loss)" if args.config == "c2"
-                       else f"training images/sec ({H}x{W}, {args.config})"),
-            "value": imgs_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "fp32 (fp16x3 split MFMA, power-of-two block scales; direct + Winograd convs)", "data": "synthetic",
-            "config": {"workload": workload,
-                       "global_batch": B * world, "image_size": [H, W], "parallelism": f"dp{world}"},
-            "roofline": None,
+        out = headline(args, world, imgs_per_s, ms, workload, final_loss)
+        out.update({
             "roofline_gemm": {"bound": "mfma", "kernel": ("gemm_nt_h3_bk32_kernel<128, 128|64>" if h3 else
                                                      "gemm_nt_x6_bk32_kernel<128, 128|64>" if x6 else
                                                      "gemm_nt_kernel<128, 128|64>")
@@ -862,10 +924,9 @@ def main():
                              "two halo rows per band re-read from L2 / MALL are not algorithmic",
                     "measured": "live over the timed steps (HIP events on the launch stream, kernel only; its "
                                 "one-block finalize launch follows)"}} if nh_launch else {})),
-            "final_loss": float(loss.item()),
             # context for the HBM rooflines above (priced against 8 TB/s): this box's streaming rate
             "hbm_probe": hbm,
-        }
+        })
         for r in (out["roofline_loss"].get("head_loss_fwd_kernel_live"), fused_roof):
             if r:
                 r["frac_of_hbm_probe"] = r["achieved"] / hbm["achieved"]

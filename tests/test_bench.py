@@ -1,5 +1,6 @@
 """bench.py: the algorithmic work it prices the step with and, on the GPU, the
-one-line JSON contract (metric, whole-job value, roofline with the dominant kernel, cpu_baseline)."""
+one-line JSON contract: the headline of a plain run (and its --dump-outputs files), and with --full
+the roofline with the dominant kernel, the probes and the distributed fields."""
 import importlib.util
 import json
 import math
@@ -27,7 +28,7 @@ def test_conv_flops_per_image(size, gflop):
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline"], capture_output=True, text=True, timeout=110, cwd=HERE)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -64,11 +65,51 @@ def test_bench_json_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline only (no roofline, probe or baseline ran), --steps
+    is the number of timed steps, and --dump-outputs writes the last step's arrays as float32 / float64
+    .npy files of at most 64 MB in all."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                          "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=110, cwd=HERE)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+              "scaling", "vs_baseline", "dtype", "data", "config", "final_loss"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+    assert d["unit"] == "images/s" and d["dtype"].startswith("fp32") and d["ms_per_step"] > 0
+    assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["roofline"] is None
+    assert not [k for k in d if k.startswith("roofline_") or k in ("cpu_baseline", "hbm_probe", "distributed")]
+    arrays = {p.stem: np.load(p) for p in dump.iterdir()}
+    assert sorted(arrays) == ["grads_sample", "loss", "params_sample", "u"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 << 20
+    assert arrays["u"].shape == (8, 1, 512, 512) and 0.0 <= arrays["u"].min() and arrays["u"].max() <= 1.0
+    assert float(arrays["loss"]) == pytest.approx(d["final_loss"], rel=1e-6)
+    assert np.abs(arrays["grads_sample"]).max() > 0 and np.abs(arrays["params_sample"]).max() > 0
+
+
+def test_bench_inputs_are_the_same_every_run():
+    """The batch depends on nothing but its fixed seed (and the rank)."""
+    import torch
+    b = _bench()
+    b.H = b.W = 64
+    x0, t0 = b.make_batch(0, "cpu")
+    x1, t1 = b.make_batch(0, "cpu")
+    assert torch.equal(x0, x1) and torch.equal(t0, t1) and x0.shape == (8, 1, 64, 64)
+
+
+@pytest.mark.gpu
 def test_bench_launches_n_ranks():
     """`bench.py --gpus 2` without a torchrun environment starts its own two ranks (here both on
     the one GPU over gloo: RCCL needs a GPU per rank) and reports the whole job."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
                           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=110, cwd=HERE, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -96,7 +137,7 @@ def test_bench_launches_n_ranks():
 def test_bench_other_config_reports_no_c2_counters():
     """A --config other than C2 must not carry C2's committed PMC counters as its own (VERDICT r5
     weak #11): traffic / MFMA-busy fields are null and the line says why."""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--config", "c4-rd", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--full", "--config", "c4-rd", "--steps", "2",
                           "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=110, cwd=HERE)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

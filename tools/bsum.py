@@ -7,6 +7,9 @@ for path in sys.argv[1:]:
         if not ln.startswith("{"):
             continue
         d = json.loads(ln)
+        if "roofline_gemm" not in d:  # a plain run (no --full): the headline only
+            print(f"{path}: {d['value']:.1f} img/s {d['ms_per_step']:.3f} ms")
+            continue
         rl = d.get("roofline_loss", {})
         hk = rl.get("head_loss_fwd_kernel_live", {})
         hc = rl.get("head_loss_fwd_live", {})

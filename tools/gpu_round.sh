@@ -31,7 +31,7 @@ if [ "$MODE" = tests ]; then
   step pytest_gpu 1200 python -u -m pytest tests -m gpu -v --timeout 400 --timeout-method thread
 fi
 if [ "$BENCH" = bench ]; then
-  step bench 400 python -u bench.py
+  step bench 400 python -u bench.py --full
 fi
 step rocprof_stats 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline
 step pmc_fetch 120 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
