@@ -478,6 +478,27 @@ int pis_synth_discs(const float* discs, const int* ndisc, int max_discs, uint64_
                     const int64_t* sample_ids, float* img, float* mask, int B, int H, int W,
                     void* ws, size_t ws_bytes, pis_stream_t stream);
 
+/* ---- boundary F1 / Hausdorff counters of a batch (src/evaluate.py:102-275), exact ----
+ * p: probabilities, t: masks, both (B, H, W) fp32. Foreground is p > thr (strict; NaN is
+ * background) and t > 0. The boundary set of an image is its foreground pixels with a
+ * 4-neighbour in the outer background: the 4-connected background component that touches a
+ * zero frame around the image (out-of-image neighbours count); holes and whatever is nested in
+ * them contribute nothing. With Bp, Bt the boundary sets of sample b and d(q, X) the Euclidean
+ * distance from pixel q to the nearest pixel of X,
+ *   counts[b] = { n_p = |Bp|, n_t = |Bt|,
+ *                 m_p = #{q in Bp : d(q, Bt)^2 <= tolerance^2}, m_t = #{q in Bt : d(q, Bp)^2 <= tolerance^2},
+ *                 h2_pt = max_{q in Bp} d(q, Bt)^2, h2_tp = max_{q in Bt} d(q, Bp)^2 }
+ * all exact integers (m_* = 0 and h2_* = -1 when either set is empty), independent of launch
+ * order and bitwise reproducible. bnd_p / bnd_t (each may be NULL) receive the boundary maps as
+ * uint8 (B, H, W). B >= 1, 1 <= H, W <= 4096, tolerance >= 0; anything else is PIS_ERR_ARG, a
+ * workspace below pis_boundary_ws(B, H, W) bytes PIS_ERR_WORKSPACE (pis_boundary_ws is 0 for an
+ * unsupported shape). A fixed sequence of launches on `stream`, no host synchronisation, no
+ * state in ws between calls. */
+size_t pis_boundary_ws(int B, int H, int W);
+int pis_boundary_metrics(const float* p, const float* t, int B, int H, int W, float thr, int tolerance,
+                         int* counts, uint8_t* bnd_p, uint8_t* bnd_t, void* ws, size_t ws_bytes,
+                         pis_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

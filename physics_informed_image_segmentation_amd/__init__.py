@@ -11,9 +11,10 @@ matplotlib plotting helpers of src/plot.py (out of scope).
 __version__ = "0.2.0"
 
 from .dataset import CellSegmentationDataset, SyntheticDiscDataset  # noqa: E402
-from .evaluate import (compare_models_statistically, compute_boundary_f1, compute_boundary_f1_batch,  # noqa: E402
-                       compute_hausdorff_distance, compute_iou, compute_iou_batch, compute_statistics,
-                       evaluate_model, evaluate_on_test_set, format_metric_report)
+from .evaluate import (boundary_counts, compare_models_statistically, compute_boundary_f1,  # noqa: E402
+                       compute_boundary_f1_batch, compute_hausdorff_distance, compute_hausdorff_distance_batch,
+                       compute_iou, compute_iou_batch, compute_statistics, evaluate_model, evaluate_on_test_set,
+                       extract_boundaries_device, format_metric_report)
 from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
@@ -30,4 +31,5 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "compare_models_statistically", "format_metric_report", "compute_statistics", "evaluate_and_compare",
            "run_repeated_evaluations", "AblationConfig", "run_ablation_variant", "run_ablation_study",
            # build additions
-           "SyntheticDiscDataset", "count_parameters", "train_epoch", "AdamW"]
+           "SyntheticDiscDataset", "count_parameters", "train_epoch", "AdamW", "boundary_counts",
+           "extract_boundaries_device", "compute_hausdorff_distance_batch"]

@@ -96,6 +96,8 @@ _SIGNATURES = {
     "pis_pde_fields_bwd": ([P, P, P, P, I, I, I, c_float, c_float, P, P], c_int),
     "pis_synth_ws": ([I, I, I], c_size_t),
     "pis_synth_discs": ([P, P, I, ctypes.c_uint64, P, P, P, I, I, I, P, Z, P], c_int),
+    "pis_boundary_ws": ([I, I, I], c_size_t),
+    "pis_boundary_metrics": ([P, P, I, I, I, c_float, I, P, P, P, P, Z, P], c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -17,16 +17,30 @@
     - Hausdorff = scipy's directed_hausdorff both ways on the boundary coordinates (:232-275).
   Parity for these two is unpinned against OpenCV itself (absent); tests/test_host.py pins
   them on hand-drawn shapes with known contours.
+* The same two metrics run on the GPU for CUDA tensors (csrc/boundary.hip, pis_boundary_metrics):
+  a whole batch per call, a fixed number of launches on the current stream, no host
+  synchronisation. Everything in them is integer geometry, so the device path returns the host
+  path's boundary maps, counters and squared Hausdorff distances EXACTLY (tests/test_boundary_gpu.py
+  compares with ==): outer background by union-find over background pixels with a virtual frame
+  node, then per boundary pixel the exact squared distance to the other boundary set from a
+  column-distance map. The host dilation tests are Euclidean-disk tests, so one distance pass
+  gives both the tolerance counters of boundary F1 and the directed Hausdorff distances.
+  ``boundary_counts`` / ``extract_boundaries_device`` / ``compute_hausdorff_distance_batch`` are
+  the device entry points; ``compute_boundary_f1_batch``, ``compute_boundary_f1`` and
+  ``compute_hausdorff_distance`` take ``backend="auto" | "host" | "device"`` ("auto": device when
+  both tensors are CUDA tensors). The host functions are unchanged and are the tests' oracle.
 """
 from __future__ import annotations
 
-from typing import Dict
+import ctypes
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 from scipy import ndimage
 from scipy.spatial.distance import directed_hausdorff
 
+from . import _hip
 from .metrics import compute_dice_score_batch, sample_counts
 
 _FOUR = ndimage.generate_binary_structure(2, 1)
@@ -96,27 +110,117 @@ def _boundary_f1_np(pred_b: np.ndarray, target_b: np.ndarray, tolerance: int, sm
     inter = (pred_b * target_b).sum()
     return float((2.0 * inter + smooth) / (pred_b.sum() + target_b.sum() + smooth))
 
+# ----------------------------------------------------------------------------
+# Device path (csrc/boundary.hip)
+# ----------------------------------------------------------------------------
+
+def _use_device(backend: str, predictions: torch.Tensor, targets: torch.Tensor) -> bool:
+    if backend not in ("auto", "host", "device"):
+        raise ValueError(f"backend must be 'auto', 'host' or 'device', got {backend!r}")
+    both = predictions.is_cuda and targets.is_cuda
+    if backend == "device" and not both:
+        raise ValueError(f"backend='device' needs CUDA tensors (got {predictions.device}, {targets.device})")
+    return both and backend != "host"
+
+
+def _bhw(x: torch.Tensor) -> torch.Tensor:
+    """(B, 1, H, W) / (B, H, W) / (H, W) -> contiguous fp32 (B, H, W)."""
+    x = x.detach()
+    if x.dim() < 2:
+        raise ValueError(f"need (..., H, W), got {tuple(x.shape)}")
+    H, W = x.shape[-2], x.shape[-1]
+    return x.reshape(-1, H, W).to(torch.float32).contiguous()
+
+
+def _boundary_device(predictions: torch.Tensor, targets: torch.Tensor, threshold: float, tolerance: int,
+                     maps: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One pis_boundary_metrics call on the current stream: (counts, bnd_p, bnd_t)."""
+    p, t = _bhw(predictions), _bhw(targets)
+    _hip.require_cuda(p, "boundary_counts")
+    _hip.require_cuda(t, "boundary_counts")
+    if p.shape != t.shape or p.device != t.device:
+        raise ValueError(f"predictions {tuple(p.shape)} on {p.device} and targets {tuple(t.shape)} on {t.device} differ")
+    B, H, W = p.shape
+    with torch.cuda.device(p.device):
+        nbytes = _hip.lib().pis_boundary_ws(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"boundary_counts: unsupported shape B={B} H={H} W={W} (B >= 1, 1 <= H, W <= 4096)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+        counts = torch.empty((B, 6), dtype=torch.int32, device=p.device)
+        bp = torch.empty((B, H, W), dtype=torch.uint8, device=p.device) if maps else None
+        bt = torch.empty((B, H, W), dtype=torch.uint8, device=p.device) if maps else None
+        _hip.call("pis_boundary_metrics", _hip.ptr(p), _hip.ptr(t), B, H, W, ctypes.c_float(float(threshold)),
+                  int(tolerance), _hip.ptr(counts), _hip.ptr(bp), _hip.ptr(bt), _hip.ptr(ws), nbytes,
+                  _hip.stream_handle(p.device))
+    return counts, bp, bt
+
+
+def boundary_counts(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
+                    tolerance: int = 2) -> torch.Tensor:
+    """(B, 6) int32 device tensor (n_p, n_t, m_p, m_t, h2_pt, h2_tp) per sample: boundary sizes,
+    boundary pixels within ``tolerance`` of the other boundary, squared directed Hausdorff
+    distances (-1 when either boundary is empty). Exact; no host synchronisation."""
+    return _boundary_device(predictions, targets, threshold, tolerance)[0]
+
+
+def extract_boundaries_device(mask_batch: torch.Tensor) -> torch.Tensor:
+    """``extract_boundaries`` of every (H, W) mask of a CUDA batch, as uint8 (B, H, W)."""
+    return _boundary_device(mask_batch, mask_batch, 0.0, 0, maps=True)[1]
+
+
+def _f1_from_counts(counts: torch.Tensor, tolerance: int, smooth: float) -> torch.Tensor:
+    """``_boundary_f1_np`` on the four counters, float64 on the counters' device."""
+    n_p, n_t, m_p, m_t = counts[:, :4].to(torch.float64).unbind(dim=1)
+    if tolerance > 0:
+        precision = (m_p + smooth) / (n_p + smooth)
+        recall = (m_t + smooth) / (n_t + smooth)
+        return (2.0 * precision * recall + smooth) / (precision + recall + smooth)
+    return (2.0 * m_p + smooth) / (n_p + n_t + smooth)
+
+
+def _hausdorff_from_counts(counts: torch.Tensor) -> torch.Tensor:
+    h2 = torch.maximum(counts[:, 4], counts[:, 5]).to(torch.float64)
+    return torch.where(h2 < 0, torch.full_like(h2, float("inf")), h2.clamp_min(0).sqrt())
+
+
+def compute_hausdorff_distance_batch(predictions: torch.Tensor, targets: torch.Tensor,
+                                     threshold: float = 0.5) -> torch.Tensor:
+    """Per-sample symmetric Hausdorff distance of the boundaries as a float64 device tensor; inf
+    when one boundary is empty. The squared distances are exact integers, so each entry is the
+    square root scipy's directed_hausdorff takes."""
+    return _hausdorff_from_counts(boundary_counts(predictions, targets, threshold, 0))
+
 
 def compute_boundary_f1(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
-                        tolerance: int = 2, smooth: float = 1e-6) -> torch.Tensor:
+                        tolerance: int = 2, smooth: float = 1e-6, backend: str = "auto") -> torch.Tensor:
     """Boundary F1 of the first sample within ``tolerance`` pixels (src/evaluate.py:123-182)."""
+    if _use_device(backend, predictions, targets):
+        counts = boundary_counts(predictions[0, 0], targets[0, 0], threshold, tolerance)
+        return _f1_from_counts(counts, tolerance, smooth)[0].to(torch.float32)
     pb = extract_boundaries(_binary_np(predictions[0, 0], threshold))
     tb = extract_boundaries(_binary_np(targets[0, 0]))
     return torch.tensor(_boundary_f1_np(pb, tb, tolerance, smooth), dtype=torch.float32)
 
 
 def compute_boundary_f1_batch(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
-                              tolerance: int = 2, smooth: float = 1e-6) -> torch.Tensor:
-    """Per-sample boundary F1 (src/evaluate.py:185-215); one device->host copy per batch."""
+                              tolerance: int = 2, smooth: float = 1e-6, backend: str = "auto") -> torch.Tensor:
+    """Per-sample boundary F1 (src/evaluate.py:185-215). Host path: one device->host copy per
+    batch, a CPU tensor. Device path: a tensor on the inputs' device, no host synchronisation."""
+    if _use_device(backend, predictions, targets):
+        return _f1_from_counts(boundary_counts(predictions, targets, threshold, tolerance), tolerance,
+                               smooth).to(torch.float32)
     p = (predictions.detach() > threshold).reshape(predictions.shape[0], *predictions.shape[-2:]).cpu().numpy()
     t = targets.detach().reshape(targets.shape[0], *targets.shape[-2:]).cpu().numpy()
     return torch.tensor([_boundary_f1_np(extract_boundaries(p[i]), extract_boundaries(t[i]), tolerance, smooth)
                          for i in range(p.shape[0])], dtype=torch.float32)
 
 
-def compute_hausdorff_distance(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5) -> float:
+def compute_hausdorff_distance(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
+                               backend: str = "auto") -> float:
     """Symmetric Hausdorff distance of the first sample's boundaries; inf when one is
     empty (src/evaluate.py:218-275)."""
+    if _use_device(backend, predictions, targets):
+        return float(compute_hausdorff_distance_batch(predictions[0, 0], targets[0, 0], threshold)[0])
     pc = np.column_stack(np.where(extract_boundaries(_binary_np(predictions[0, 0], threshold)) > 0))
     tc = np.column_stack(np.where(extract_boundaries(_binary_np(targets[0, 0])) > 0))
     if len(pc) == 0 or len(tc) == 0:
@@ -125,10 +229,12 @@ def compute_hausdorff_distance(predictions: torch.Tensor, targets: torch.Tensor,
 
 
 @torch.no_grad()
-def evaluate_model(model, dataloader, device, threshold: float = 0.5,
-                   boundary_metrics: bool = True) -> Dict[str, np.ndarray]:
-    """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff (host)
-    over a loader (src/evaluate.py:279-350)."""
+def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_metrics: bool = True,
+                   boundary_backend: str = "auto") -> Dict[str, np.ndarray]:
+    """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
+    (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
+    ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
+    "host" or "device", as ``compute_boundary_f1_batch``)."""
     model.eval()
     dice, iou, bf1, hd = [], [], [], []
     for images, masks in dataloader:
@@ -138,10 +244,18 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5,
         s = scores.cpu().numpy()
         dice.extend(s[:, 0].tolist())
         iou.extend(s[:, 1].tolist())
-        if boundary_metrics:
-            bf1.extend(compute_boundary_f1_batch(outputs, masks, threshold=threshold, tolerance=2).tolist())
+        if boundary_metrics and _use_device(boundary_backend, outputs, masks):
+            counts = boundary_counts(outputs, masks, threshold, 2)
+            both = torch.stack([_f1_from_counts(counts, 2, 1e-6).to(torch.float32).to(torch.float64),
+                                _hausdorff_from_counts(counts)]).cpu().numpy()
+            bf1.extend(both[0].tolist())
+            hd.extend(np.where(np.isfinite(both[1]), both[1], np.nan).tolist())
+        elif boundary_metrics:
+            bf1.extend(compute_boundary_f1_batch(outputs, masks, threshold=threshold, tolerance=2,
+                                                 backend="host").tolist())
             for i in range(outputs.shape[0]):
-                h = compute_hausdorff_distance(outputs[i:i + 1], masks[i:i + 1], threshold=threshold)
+                h = compute_hausdorff_distance(outputs[i:i + 1], masks[i:i + 1], threshold=threshold,
+                                               backend="host")
                 hd.append(h if np.isfinite(h) else np.nan)
     out = {"dice_scores": np.array(dice), "iou_scores": np.array(iou)}
     if boundary_metrics:
@@ -220,6 +334,7 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
 
 
 __all__ = ["compute_iou", "compute_iou_batch", "extract_boundaries", "compute_boundary_f1",
-           "compute_boundary_f1_batch", "compute_hausdorff_distance", "evaluate_model",
+           "compute_boundary_f1_batch", "compute_hausdorff_distance", "boundary_counts",
+           "extract_boundaries_device", "compute_hausdorff_distance_batch", "evaluate_model",
            "compute_dice_score_batch", "compute_statistics", "compare_models_statistically",
            "format_metric_report", "evaluate_on_test_set"]

@@ -14,7 +14,9 @@ What changes underneath:
     (the reference calls ``.item()``/``.cpu()`` several times per step);
   * optional data-parallel training (torchrun, RCCL), see ``distributed``;
   * boundary F1 (OpenCV in the reference, a cv2-free restatement here) is
-    scored on host threads beside the GPU, not inside the step.
+    scored on the GPU in the step's stream (``_BoundaryF1Device``,
+    csrc/boundary.hip); for host tensors or ``boundary_backend="host"`` on
+    host threads beside the GPU (``_BoundaryF1Async``).
 """
 from __future__ import annotations
 
@@ -112,7 +114,7 @@ class _Meter:
         self.terms = torch.zeros(5, dtype=torch.float64, device=device)
         self.scores = torch.zeros(2, dtype=torch.float64, device=device)
         self.batch_dice = torch.zeros(1, dtype=torch.float64, device=device)
-        self.bf1 = torch.zeros(1, dtype=torch.float64, device=device)  # host-computed boundary F1 sums
+        self.bf1 = torch.zeros(1, dtype=torch.float64, device=device)  # boundary F1 sums
         self.batches = 0
         self.samples = 0
 
@@ -153,7 +155,7 @@ def _results(meter: _Meter, criterion, return_components: bool, compute_metrics:
         if not val:
             out["dice_score"] = scores[0] / ns if ns else 0.0
         out["iou_score"] = scores[1] / ns if ns else 0.0
-        # host threads beside the GPU (_BoundaryF1Async); 0.0 with boundary_metrics=False
+        # _BoundaryF1Device / _BoundaryF1Async; 0.0 with boundary_metrics=False
         out["boundary_f1_score"] = meter.bf1_total / ns if ns else 0.0
     return out
 
@@ -238,15 +240,53 @@ class _BoundaryF1Async:
         self.pool.shutdown(wait=True)
 
 
+class _BoundaryF1Device:
+    """The same scorer on the GPU (evaluate.boundary_counts, csrc/boundary.hip): ``submit``
+    launches the batch's counters on the current stream right after the forward (the engine's
+    probability buffer is still live: the backward that reuses it is queued behind) and adds the
+    batch's float64 F1 sum into a device scalar. No copy stream, no fence, no threads, no host
+    synchronisation; ``collect`` hands the scalar to ``_Meter.bf1``."""
+
+    def __init__(self, device):
+        self.total = torch.zeros(1, dtype=torch.float64, device=device)
+
+    def before_forward(self):
+        pass
+
+    def submit(self, outputs: torch.Tensor, masks: torch.Tensor):
+        from .evaluate import _f1_from_counts, boundary_counts
+        self.total += _f1_from_counts(boundary_counts(outputs, masks, 0.5, 2), 2, 1e-6).sum()
+
+    def collect(self) -> torch.Tensor:
+        tot, self.total = self.total, torch.zeros_like(self.total)
+        return tot
+
+    def close(self):
+        pass
+
+
+def _boundary_scorer(device, backend: str):
+    """``backend``: "auto" (device scorer for a CUDA ``device``, host threads otherwise), "host"
+    or "device" (a CUDA device is required)."""
+    if backend not in ("auto", "host", "device"):
+        raise ValueError(f"boundary_backend must be 'auto', 'host' or 'device', got {backend!r}")
+    cuda = torch.device(device).type == "cuda"
+    if backend == "device" and not cuda:
+        raise ValueError(f"boundary_backend='device' needs a CUDA device (got {device})")
+    return _BoundaryF1Device(device) if cuda and backend != "host" else _BoundaryF1Async(device)
+
+
 def train_epoch(model, dataloader, criterion, optimizer, device, return_components: bool = False,
-                compute_metrics: bool = True, boundary_metrics: bool = True) -> Dict[str, float]:
+                compute_metrics: bool = True, boundary_metrics: bool = True,
+                boundary_backend: str = "auto") -> Dict[str, float]:
     """One pass over ``dataloader`` (src/train.py:84-185); same result keys and averaging:
     loss terms averaged over batches, Dice / IoU / boundary F1 over samples. Boundary F1
-    (src/train.py:156) is scored on host threads beside the GPU (``_BoundaryF1Async``);
-    ``boundary_metrics=False`` reports 0.0 instead."""
+    (src/train.py:156) is scored on the GPU in the step's stream (``_BoundaryF1Device``) or, for
+    host tensors and ``boundary_backend="host"``, on host threads beside the GPU
+    (``_BoundaryF1Async``); ``boundary_metrics=False`` reports 0.0 instead."""
     model.train()
     meter = _Meter(device)
-    bf1 = _BoundaryF1Async(device) if compute_metrics and boundary_metrics else None
+    bf1 = _boundary_scorer(device, boundary_backend) if compute_metrics and boundary_metrics else None
     try:
         for images, masks in dataloader:
             images = images.to(device, non_blocking=True)
@@ -271,12 +311,13 @@ def train_epoch(model, dataloader, criterion, optimizer, device, return_componen
 
 @torch.no_grad()
 def validate(model, dataloader, criterion, device, return_components: bool = False,
-             compute_metrics: bool = True, boundary_metrics: bool = True) -> Dict[str, float]:
+             compute_metrics: bool = True, boundary_metrics: bool = True,
+             boundary_backend: str = "auto") -> Dict[str, float]:
     """Eval-mode pass (src/train.py:188-286); ``dice_score`` is the mean of
-    whole-batch thresholded Dice, as in the reference."""
+    whole-batch thresholded Dice, as in the reference. ``boundary_backend`` as in ``train_epoch``."""
     model.eval()
     meter = _Meter(device)
-    bf1 = _BoundaryF1Async(device) if compute_metrics and boundary_metrics else None
+    bf1 = _boundary_scorer(device, boundary_backend) if compute_metrics and boundary_metrics else None
     try:
         for images, masks in dataloader:
             images = images.to(device, non_blocking=True)
