@@ -204,7 +204,16 @@ int pis_version(void);
                                      4 (any other value) one block per CU, the next tile's loads in registers.
                                      2 vs 4: -2..-10 % per layer isolated, step 22.08 -> 21.76 ms
                                      (profiles/r6_d1_direct_wgrad_rows.txt) */
-#define PIS_TUNE_NKEYS 50
+#define PIS_TUNE_WINO_XFORM 50 /* the F(4x4) input transform and merged dz pass (csrc/winograd.hip
+                                  wino4_input_cols_kernel / wino4_dz2_cols_kernel): 1 (default) the whole 6 x 6
+                                  patch in one branch-free load phase (clamped coordinates, the border ring
+                                  zeroed by a select), outputs produced column by column and stored as
+                                  produced, E from the patch's interior (bitwise equal: same sums in the same
+                                  order; dz2 162 -> 111 VGPRs, 140 -> 117 us per launch); 0 the row-by-row
+                                  kernels (a full memory wait per patch row, the interior read twice);
+                                  2 / 4: the dz pass / the input transform alone (the per-part A/B,
+                                  profiles/r7_ab_wino_xform.txt) */
+#define PIS_TUNE_NKEYS 51
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,

@@ -385,10 +385,11 @@ __global__ __launch_bounds__(256) void wino4_filter_kernel(const float* __restri
 // 32 n x 32 c; the 9 taps of that tile are read along n (128-B runs of the original [C][9][N]
 // weights) into LDS and each thread then transforms (n, c) pairs with c fastest, so the 36
 // output planes are written in runs along c as by wino4_filter_kernel.
+// sg: the calling kernel's one tap tile (the batch kernel shares it between the tile families)
+using FilterTapTile = float[9][32][33];  // [tap][c][n], padded: the transform reads along c conflict-free
 __device__ __forceinline__ void wino4_filter_rot_tile(const float* __restrict__ w, int N, int C,
                                                       float* __restrict__ U, int transposed,
-                                                      __bf16* __restrict__ Up, int tile) {
-  __shared__ float sg[9][32][33];  // [tap][c][n], padded: the transform reads along c conflict-free
+                                                      __bf16* __restrict__ Up, int tile, FilterTapTile& sg) {
   const int nb = N / 32, n0 = 32 * (tile % nb), c0 = 32 * (tile / nb);
   const int tid = threadIdx.x, lx = tid & 31, ly = tid >> 5;
 #pragma unroll
@@ -413,7 +414,8 @@ __device__ __forceinline__ void wino4_filter_rot_tile(const float* __restrict__ 
 __global__ __launch_bounds__(256) void wino4_filter_rot_kernel(const float* __restrict__ w, int N, int C,
                                                                float* __restrict__ U, int transposed,
                                                                __bf16* __restrict__ Up) {
-  wino4_filter_rot_tile(w, N, C, U, transposed, Up, blockIdx.x);
+  __shared__ FilterTapTile sg;
+  wino4_filter_rot_tile(w, N, C, U, transposed, Up, blockIdx.x, sg);
 }
 
 // The fused kernel's fp16x3 filter planes (pis_tune key 22), C % 64 == 0: one wave per output
@@ -564,8 +566,7 @@ __device__ __forceinline__ void wino6_filter_range(const float* __restrict__ w, 
 // the input gradient's transform straight from the layer's ORIGINAL weights [C][9][N] (N = Cin,
 // C = Cout; rotated and transposed in place, as wino4_filter_rot_tile): a block owns 32 n x 32 c
 __device__ __forceinline__ void wino6_filter_rot_tile(const float* __restrict__ w, int N, int C, float* __restrict__ U,
-                                                      int tile) {
-  __shared__ float sg[9][32][33];  // [tap][c][n]
+                                                      int tile, FilterTapTile& sg) {
   const int nb = N / 32, n0 = 32 * (tile % nb), c0 = 32 * (tile / nb);
   const int tid = threadIdx.x, lx = tid & 31, ly = tid >> 5;
 #pragma unroll
@@ -593,7 +594,8 @@ __global__ __launch_bounds__(256) void wino6_filter_kernel(const float* __restri
 }
 __global__ __launch_bounds__(256) void wino6_filter_rot_kernel(const float* __restrict__ w, int N, int C,
                                                                float* __restrict__ U) {
-  wino6_filter_rot_tile(w, N, C, U, blockIdx.x);
+  __shared__ FilterTapTile sg;
+  wino6_filter_rot_tile(w, N, C, U, blockIdx.x, sg);
 }
 
 // V[xi][t][c] = (BT d BT^T)[xi], d = the 8 x 8 input patch at rows 6 ty - 1 .., cols 6 tx - 1 ..
@@ -814,6 +816,7 @@ struct FilterBatch {
 };
 
 __global__ __launch_bounds__(256) void wino4_filter_batch_kernel(FilterBatch fb) {
+  __shared__ FilterTapTile sg;  // one tap tile for both rotating tile families (a block runs one job)
   int k = 0;
   while (k + 1 < fb.n && (int)blockIdx.x >= fb.start[k + 1]) ++k;
   const FilterJobDev& jb = fb.j[k];
@@ -821,10 +824,10 @@ __global__ __launch_bounds__(256) void wino4_filter_batch_kernel(FilterBatch fb)
   float* U = jb.planes ? nullptr : reinterpret_cast<float*>(jb.out);
   __bf16* Up = jb.planes ? reinterpret_cast<__bf16*>(jb.out) : nullptr;
   if (jb.tile == 6) {
-    if (jb.dgrad) wino6_filter_rot_tile(jb.w, jb.N, jb.C, U, lb);
+    if (jb.dgrad) wino6_filter_rot_tile(jb.w, jb.N, jb.C, U, lb, sg);
     else wino6_filter_range(jb.w, 9 * jb.C, jb.N, jb.C, U, lb, jb.blocks);
   } else if (jb.planes == 2) wino4_filter_h2_wave(jb.w, 9 * jb.C, jb.N, jb.C, jb.dgrad, Up, 4 * lb + (threadIdx.x >> 6));
-  else if (jb.dgrad) wino4_filter_rot_tile(jb.w, jb.N, jb.C, U, 0, Up, lb);
+  else if (jb.dgrad) wino4_filter_rot_tile(jb.w, jb.N, jb.C, U, 0, Up, lb, sg);
   else wino4_filter_range(jb.w, 9 * jb.C, jb.N, jb.C, U, 0, Up, lb, jb.blocks);
 }
 
@@ -1074,6 +1077,144 @@ __global__ __launch_bounds__(256) void wino4_dz2_kernel(const float* __restrict_
     const float m = wino4_input_item<VW, TM>(dz, ldz, H, W, N, V, TN, t, b, ty, tx, n);
     if constexpr (TM) tile_max_store<VW>(m, N, n, t, tmax);
     wino4_dz_item<VW>(dz, ldz, H, W, N, E, TN, t, b, ty, tx, n, bsum);
+  }
+  if (bpart) wino4_bias_partials<VW>(bsum, N, bpart);
+}
+
+// ---- single-load-phase forms of the F(4x4) input transform and merged dz pass (pis_tune key
+// 50 = 1, default; the output transform gained nothing from the same form) ----
+// The row-by-row kernels above keep 36 accumulators and one patch row live; every row's loads
+// sit behind bounds-check branches and a full wait, which also drains the stores issued before
+// it (7 serialized memory round trips per dz2 item, and the interior read twice). Here the whole
+// 6 x 6 patch is loaded first, branch-free (clamped coordinates, then the border ring zeroed by a
+// select), and the outputs are produced one column j at a time and stored as produced:
+// V[i][j] = sum_k bt(i,k) r[k], r[k] = sum_l bt(j,l) d[k][l] — per output the same sums in the
+// same order as the row forms, so the results are bitwise theirs.
+template <int VW>
+__device__ __forceinline__ void wino4_patch_load(const float* __restrict__ x, int ldx, int H, int W, int b, int ty,
+                                                 int tx, int c, fvec<VW> (&d)[6][6]) {
+  // H % 4 == W % 4 == 0: only patch row / column 0 (first tile row / column) and 5 (last) can
+  // fall outside the image
+  const bool top = ty == 0, bot = 4 * ty + 4 >= H, lef = tx == 0, rig = 4 * tx + 4 >= W;
+  const float* p = x + (size_t)b * H * W * ldx + c;
+  size_t ro[6], co[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int h = 4 * ty - 1 + k, ww = 4 * tx - 1 + k;
+    ro[k] = (size_t)(k == 0 && top ? 0 : k == 5 && bot ? H - 1 : h) * W * ldx;
+    co[k] = (size_t)(k == 0 && lef ? 0 : k == 5 && rig ? W - 1 : ww) * ldx;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+#pragma unroll
+    for (int l = 0; l < 6; ++l) d[k][l] = *reinterpret_cast<const fvec<VW>*>(p + ro[k] + co[l]);
+  __builtin_amdgcn_sched_barrier(0);  // all 36 loads issued before the first wait for one of them
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+#pragma unroll
+    for (int l = 0; l < 6; ++l) {
+      if (k != 0 && k != 5 && l != 0 && l != 5) continue;
+      const bool out = (k == 0 && top) || (k == 5 && bot) || (l == 0 && lef) || (l == 5 && rig);
+      d[k][l] = out ? (fvec<VW>)0.f : d[k][l];
+    }
+}
+
+// V = BT d BT^T of a loaded patch, column by column (wino4_input_item's sums); returns max |V| (TM)
+template <int VW, bool TM>
+__device__ __forceinline__ float wino4_input_cols(const fvec<VW> (&d)[6][6], float* __restrict__ Vo, int64_t TC) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    fvec<VW> r[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      r[k] = (fvec<VW>)0.f;
+#pragma unroll
+      for (int l = 0; l < 6; ++l) axpy_c(r[k], w4_bt(j, l), d[k][l]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      fvec<VW> v = (fvec<VW>)0.f;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) axpy_c(v, w4_bt(i, k), r[k]);
+      *reinterpret_cast<fvec<VW>*>(Vo + (size_t)(6 * i + j) * TC) = v;
+      if constexpr (TM)
+#pragma unroll
+        for (int q = 0; q < VW; ++q) m = fmaxf(m, fabsf(v[q]));
+    }
+    // the running max is pinned per column: left free, the compiler sinks all 72 comparisons
+    // below the last column and keeps every output alive for them (+50 registers)
+    if constexpr (TM) asm volatile("" : "+v"(m));
+    __builtin_amdgcn_sched_barrier(0);  // this column's stores leave before the next is computed
+  }
+  return m;
+}
+
+// E = G4 e G4^T of the patch's 4 x 4 interior, column by column, and the bias sums
+// (wino4_dz_item's sums)
+template <int VW>
+__device__ __forceinline__ void wino4_dz_cols(const fvec<VW> (&d)[6][6], float* __restrict__ Eo, int64_t TN,
+                                              fvec<VW>& bsum) {
+#pragma unroll
+  for (int k = 1; k < 5; ++k) bsum += (d[k][1] + d[k][2]) + (d[k][3] + d[k][4]);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    fvec<VW> r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      r[k] = (fvec<VW>)0.f;
+#pragma unroll
+      for (int l = 0; l < 4; ++l) axpy_c(r[k], w4_g4(j, l), d[k + 1][l + 1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      fvec<VW> v = (fvec<VW>)0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) axpy_c(v, w4_g4(i, k), r[k]);
+      *reinterpret_cast<fvec<VW>*>(Eo + (size_t)(6 * i + j) * TN) = v;
+    }
+    __builtin_amdgcn_sched_barrier(0);  // this column's stores leave before the next is computed
+  }
+}
+
+// wino4_input_kernel, single load phase
+template <int VW, bool TM = false>
+__global__ __launch_bounds__(256) void wino4_input_cols_kernel(const float* __restrict__ x, int ldx, int B, int H,
+                                                               int W, int C, float* __restrict__ V,
+                                                               float* __restrict__ tmax = nullptr) {
+  const int c4n = C / VW, TW = W / 4, TH = H / 4;
+  const int64_t T = (int64_t)B * TH * TW, TC = T * C;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < T * c4n; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t t;
+    int c, b, rem;
+    tile_decode<VW>(e, c4n, TH * TW, t, c, b, rem);
+    const int ty = rem / TW, tx = rem - ty * TW;
+    fvec<VW> d[6][6];
+    wino4_patch_load<VW>(x, ldx, H, W, b, ty, tx, c, d);
+    const float m = wino4_input_cols<VW, TM>(d, V + t * C + c, TC);
+    if constexpr (TM) tile_max_store<VW>(m, C, c, t, tmax);
+  }
+}
+
+// wino4_dz2_kernel, single load phase: one read of the patch serves E (its interior) and V
+template <bool TM = false, int VW = 4>
+__global__ __launch_bounds__(256) void wino4_dz2_cols_kernel(const float* __restrict__ dz, int ldz, int B, int H,
+                                                             int W, int N, float* __restrict__ V,
+                                                             float* __restrict__ E, float* __restrict__ bpart,
+                                                             float* __restrict__ tmax = nullptr) {
+  const int nvn = N / VW, TW = W / 4, TH = H / 4;
+  const int64_t T = (int64_t)B * TH * TW, TN = T * N;
+  fvec<VW> bsum = (fvec<VW>)0.f;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < T * nvn; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t t;
+    int n, b, rem;
+    tile_decode<VW>(e, nvn, TH * TW, t, n, b, rem);
+    const int ty = rem / TW, tx = rem - ty * TW;
+    fvec<VW> d[6][6];
+    wino4_patch_load<VW>(dz, ldz, H, W, b, ty, tx, n, d);
+    wino4_dz_cols<VW>(d, E + t * N + n, TN, bsum);
+    const float m = wino4_input_cols<VW, TM>(d, V + t * N + n, TN);
+    if constexpr (TM) tile_max_store<VW>(m, N, n, t, tmax);
   }
   if (bpart) wino4_bias_partials<VW>(bsum, N, bpart);
 }
@@ -2209,23 +2350,31 @@ static void launch_wino4_output(const float* Mt, const IGemmArgs& a, int B, int6
     hipLaunchKernelGGL(wino4_output_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B);
 }
 
+// which of the F(4x4) input-side transforms take their single-load-phase form (pis_tune key 50):
+// 1 (default) both, 0 neither; 2 / 4 the merged dz pass / the input transform alone
+enum { XF_DZ2 = 2, XF_INPUT = 4 };
+static bool wino_xform(int part) {
+  const int v = tune_get(PIS_TUNE_WINO_XFORM);
+  return v == 1 || (v & part) != 0;
+}
+
 // the F(4x4,3x3) input transform, 2 (default) or 4 channels per thread (pis_tune key 17)
 // tmax (C % 64 == 0): also the per-tile, per-64-channel-chunk max |V| (the fp16x3 tile scales)
 static void launch_wino4_input(int64_t T, int C, hipStream_t s, const float* x, int ldx, int B, int H, int W, int,
                                float* V, float* tmax = nullptr) {
-  const bool vw2 = tune_get(PIS_TUNE_WINO_VW) != 4;
-  if (tmax && vw2)
-    hipLaunchKernelGGL((wino4_input_kernel<2, true>), dim3(grid_of(T * (C / 2))), dim3(256), 0, s, x, ldx, B, H, W, C,
-                       V, tmax);
-  else if (tmax)
-    hipLaunchKernelGGL((wino4_input_kernel<4, true>), dim3(grid_of(T * (C / 4))), dim3(256), 0, s, x, ldx, B, H, W, C,
-                       V, tmax);
-  else if (vw2)
-    hipLaunchKernelGGL(wino4_input_kernel<2>, dim3(grid_of(T * (C / 2))), dim3(256), 0, s, x, ldx, B, H, W, C, V,
-                       nullptr);
-  else
-    hipLaunchKernelGGL(wino4_input_kernel<4>, dim3(grid_of(T * (C / 4))), dim3(256), 0, s, x, ldx, B, H, W, C, V,
-                       nullptr);
+  const bool vw2 = tune_get(PIS_TUNE_WINO_VW) != 4, cols = wino_xform(XF_INPUT);
+  const dim3 grid(grid_of(T * (C / (vw2 ? 2 : 4))));
+#define PIS_INPUT_LAUNCH(VW, TM)                                                                                  \
+  do {                                                                                                            \
+    if (cols) hipLaunchKernelGGL((wino4_input_cols_kernel<VW, TM>), grid, dim3(256), 0, s, x, ldx, B, H, W, C, V, \
+                                 tmax);                                                                           \
+    else hipLaunchKernelGGL((wino4_input_kernel<VW, TM>), grid, dim3(256), 0, s, x, ldx, B, H, W, C, V, tmax);    \
+  } while (0)
+  if (tmax && vw2) PIS_INPUT_LAUNCH(2, true);
+  else if (tmax) PIS_INPUT_LAUNCH(4, true);
+  else if (vw2) PIS_INPUT_LAUNCH(2, false);
+  else PIS_INPUT_LAUNCH(4, false);
+#undef PIS_INPUT_LAUNCH
 }
 
 // the F(4x4,3x3) filter transform of a's weights (the tiled kernel for unflipped 32-aligned shapes)
@@ -2621,14 +2770,19 @@ int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float*
   const int64_t T = (int64_t)B * (H / 4) * (W / 4);
   const int vw = dz_vw(N);
   const dim3 grid(grid_of(T * (N / vw)));
-  if (tmax && vw == 2)
-    hipLaunchKernelGGL((wino4_dz2_kernel<true, 2>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart, tmax);
-  else if (tmax)
-    hipLaunchKernelGGL((wino4_dz2_kernel<true, 4>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart, tmax);
-  else if (vw == 2)
-    hipLaunchKernelGGL((wino4_dz2_kernel<false, 2>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart, nullptr);
-  else
-    hipLaunchKernelGGL((wino4_dz2_kernel<false, 4>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart, nullptr);
+  const bool cols = wino_xform(XF_DZ2);
+#define PIS_DZ2_LAUNCH(TM, VW)                                                                                     \
+  do {                                                                                                             \
+    if (cols) hipLaunchKernelGGL((wino4_dz2_cols_kernel<TM, VW>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, \
+                                 bpart, tmax);                                                                     \
+    else hipLaunchKernelGGL((wino4_dz2_kernel<TM, VW>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart,   \
+                            tmax);                                                                                 \
+  } while (0)
+  if (tmax && vw == 2) PIS_DZ2_LAUNCH(true, 2);
+  else if (tmax) PIS_DZ2_LAUNCH(true, 4);
+  else if (vw == 2) PIS_DZ2_LAUNCH(false, 2);
+  else PIS_DZ2_LAUNCH(false, 4);
+#undef PIS_DZ2_LAUNCH
   return launch_status("wino_dz2");
 }
 

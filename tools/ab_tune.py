@@ -1,7 +1,7 @@
 """A/B of pis_tune settings on the C2 training step, interleaved rounds in one process on one
 GPU (box-to-box variance is ~3 %; same-process interleaving is not).
 
-    python tools/ab_tune.py --variants "base;20=0;15=0,17=4" [--rounds 4] [--steps 10] [--shared]
+    python tools/ab_tune.py --variants "base;20=0;15=0,17=4" [--rounds 4] [--steps 10] [--shared] [--rotate]
 
 Each variant is a comma list of KEY=VALUE (include/pis_capi.h PIS_TUNE_*); "base" = defaults;
 "fa=0..5" plans that variant's engine with PIS_FILTER_AHEAD = that value, "dwm=0|1" runs the direct
@@ -39,6 +39,12 @@ def main():
     ap.add_argument("--shared", action="store_true",
                     help="one model (planned with the defaults) for every variant: for knobs that do not change "
                          "the engine's plan; removes the 2-3 %% placement effect of separately allocated models")
+    ap.add_argument("--rotate", action="store_true",
+                    help="start each round one variant later: a variant's place in the round (the first run after "
+                         "the pause between rounds reads fastest) then averages out over the rounds")
+    ap.add_argument("--warm", type=int, default=0,
+                    help="steps of the first variant before the first round (the step time drifts up by ~2 %% over "
+                         "the first ~20 s of load; 1500 steps reach the plateau)")
     args = ap.parse_args()
     lib = _hip.lib()
     variants = [(v.strip(), parse(v)) for v in args.variants.split(";")]
@@ -87,11 +93,19 @@ def main():
         return (time.perf_counter() - t0) / args.steps * 1e3
 
     res = {}
-    for _ in range(args.rounds):
-        for name, kv in variants:
-            res.setdefault(name, []).append(run(name, kv))
+    for name, _ in variants:
+        res[name] = []
+    setv(variants[0][1])
+    for _ in range(args.warm):
+        step(variants[0][0])
+    for r in range(args.rounds):
+        k = r % len(variants) if args.rotate else 0
+        for name, kv in variants[k:] + variants[:k]:
+            res[name].append(run(name, kv))
     for k in keys:
         lib.pis_tune(k, defaults[k])
+    for name, ms in res.items():  # in round order: for round-by-round comparisons of two variants
+        print(f"{name:16s} rounds " + " ".join(f"{m:.3f}" for m in ms), flush=True)
     for name, ms in res.items():
         ms.sort()
         med = ms[len(ms) // 2]
