@@ -30,6 +30,11 @@ def parse_args(argv=None):
                     help="Directory to save evaluation results (default: output)")
     ap.add_argument("--repeated", action="store_true",
                     help="Run repeated experiments evaluation (baseline and pde should be glob patterns)")
+    ap.add_argument("--device-cache", action="store_true",
+                    help="preprocess the test set once and serve every batch from a device-resident cache")
+    ap.add_argument("--augment", choices=["flip", "d4"], default=None,
+                    help="accepted so main.py's data flags can be passed unchanged; it applies to training "
+                         "loaders only, and evaluation has none")
     return ap.parse_args(argv)
 
 
@@ -44,6 +49,8 @@ def main(argv=None):
     print(f"Using device: {device}")
     common = dict(test_dir=Path(args.test_dir), test_json=Path(args.test_json), device=device,
                   batch_size=args.batch_size, threshold=args.threshold, output_dir=Path(args.output_dir))
+    if args.device_cache:
+        common["device_cache"] = True
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

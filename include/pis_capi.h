@@ -508,6 +508,31 @@ int pis_boundary_metrics(const float* p, const float* t, int B, int H, int W, fl
                          int* counts, uint8_t* bnd_p, uint8_t* bnd_t, void* ws, size_t ws_bytes,
                          pis_stream_t stream);
 
+/* ---- batches from a device-resident dataset cache (no reference counterpart: replaces the
+ * DataLoader workers + host-to-device copies around src/dataset.py:55-84 once the samples have been
+ * preprocessed on the host; physics_informed_image_segmentation_amd/dataset.py:DeviceCachedLoader) ----
+ * The cache holds N samples of H x W pixels, sample i at img + i * img_stride and mask + i * mask_stride
+ * (strides in bytes, multiples of 16, at least one sample long; bases 16-byte aligned):
+ *   PIS_CACHE_IMG_U8    H*W uint8 grey values; norm[i] = (lo, den) fp32, pixel = (float(v) - lo) / den in
+ *                       correctly rounded fp32 (bit-identical to the host loader's min-max)
+ *   PIS_CACHE_IMG_F32   H*W fp32, copied
+ *   PIS_CACHE_MASK_BITS one bit per pixel, pixel p = bit (p & 31) of 32-bit word p >> 5 -> 0.0f / 1.0f
+ *   PIS_CACHE_MASK_F32  H*W fp32, copied
+ * One launch writes img_out and mask_out, both (B, 1, H, W) fp32 contiguous, for the samples idx[0..B)
+ * (device memory; repeats allowed). sym == NULL: identity; else one code per batch entry (device memory),
+ * applied to image and mask alike: bit 0 flips W, bit 1 flips H, then bit 2 transposes (H == W only), i.e.
+ *   t = sample; if (s & 1) t = flip_W(t); if (s & 2) t = flip_H(t); if (s & 4) t = transpose(t).
+ * What the host cannot see never faults: an idx outside [0, N), a code above 7 or bit 2 with H != W fills
+ * that entry's two outputs with NaN and reads nothing of the cache. Unknown formats, a u8 image without
+ * norm, bad strides or alignment, B > 65535 or H * W > 2^30 are PIS_ERR_ARG. No workspace, no state. */
+#define PIS_CACHE_IMG_U8 0
+#define PIS_CACHE_IMG_F32 1
+#define PIS_CACHE_MASK_BITS 0
+#define PIS_CACHE_MASK_F32 1
+int pis_cache_batch(const void* img, int img_fmt, size_t img_stride, const void* mask, int mask_fmt,
+                    size_t mask_stride, const float* norm, const int64_t* idx, const uint8_t* sym, int64_t N,
+                    float* img_out, float* mask_out, int B, int H, int W, pis_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 """CLI of the reference (main.py:5-102): same flags and defaults, training on
-the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir."""
+the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
+--device-cache, --augment {flip,d4}."""
 import argparse
 
 from physics_informed_image_segmentation_amd.train import train
@@ -24,7 +25,16 @@ def parse_args(argv=None):
     p.add_argument("--synthetic", type=int, nargs=4, metavar=("N_TRAIN", "N_VAL", "H", "W"), default=None,
                    help="train on the synthetic disc generator instead of images/")
     p.add_argument("--base-dir", type=str, default=None, help="directory holding images/, output/, models/")
-    return p.parse_args(argv)
+    p.add_argument("--device-cache", action="store_true",
+                   help="preprocess the datasets once and serve every batch from a device-resident cache "
+                        "(with --synthetic: the host disc dataset, cached, instead of the on-GPU generator)")
+    p.add_argument("--augment", choices=["flip", "d4"], default=None,
+                   help="random flips / all 8 grid symmetries per sample and epoch on the training loader "
+                        "(needs --device-cache)")
+    a = p.parse_args(argv)
+    if a.augment and not a.device_cache:
+        p.error("--augment needs --device-cache")
+    return a
 
 
 def main(argv=None):
@@ -35,7 +45,8 @@ def main(argv=None):
                  stage1_epochs=a.stage1_epochs, stage2_epochs=a.stage2_epochs,
                  early_stopping_patience=a.early_stopping_patience, train_fraction=a.train_fraction,
                  seed=a.seed, base_dir=a.base_dir,
-                 synthetic=tuple(a.synthetic) if a.synthetic else None)
+                 synthetic=tuple(a.synthetic) if a.synthetic else None,
+                 device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment)
 
 
 if __name__ == "__main__":

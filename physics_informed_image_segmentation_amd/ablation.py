@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader
 
-from .dataset import CellSegmentationDataset, SyntheticDiscDataset
+from .dataset import CellSegmentationDataset, DeviceCachedLoader, SyntheticDiscDataset
 from .evaluate import evaluate_model
 from .fused import LossConfig, fused_loss
 from .loss import BCELoss, DiceBCELoss, DiceBCEPDELoss
@@ -252,9 +252,14 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                          learning_rate: float = 1e-4, stage1_epochs: int = 50, stage2_epochs: int = 50,
                          early_stopping_patience: int = 10, output_dir: Optional[Path] = None,
                          ablation_folder: Optional[Path] = None, num_workers: int = 2, boundary_metrics: bool = True,
-                         verbose: bool = False) -> Dict:
+                         verbose: bool = False, device_cache: bool = False, augment: Optional[str] = None) -> Dict:
     """Train one variant and evaluate it on both test sets (src/ablation.py:157-1237); same
-    positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead)."""
+    positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead).
+    ``device_cache=True`` keeps the four datasets resident on the GPU and assembles the batches there
+    (``dataset.DeviceCachedLoader``; ``augment`` on the training loader only); a set that does not fit
+    keeps its ``DataLoader``."""
+    if augment is not None and not device_cache:
+        raise ValueError("augment needs device_cache=True (the symmetries are applied by the cache kernel)")
     data = _data_spec(train_dir, (train_json, val_dir, val_json, in_dist_test_dir, in_dist_test_json,
                                   out_dist_test_dir, out_dist_test_json))
     if device is None:
@@ -270,7 +275,18 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
     if config.train_fraction is not None:
         train_ds = create_subset_dataset(train_ds, config.train_fraction)
     pin = torch.cuda.is_available()
-    mk = lambda ds, sh: DataLoader(ds, batch_size=batch_size, shuffle=sh, num_workers=num_workers, pin_memory=pin)
+
+    def mk(ds, sh):
+        if device_cache:
+            try:
+                return DeviceCachedLoader(ds, batch_size, shuffle=sh, seed=config.seed, device=device,
+                                          augment=augment if sh else None)
+            except ValueError as e:
+                if "max_bytes" not in str(e):
+                    raise
+                print(f"device cache not used, falling back to DataLoader workers: {e}")
+        return DataLoader(ds, batch_size=batch_size, shuffle=sh, num_workers=num_workers, pin_memory=pin)
+
     train_loader, val_loader = mk(train_ds, True), mk(val_ds, False)
     in_loader, out_loader = mk(in_ds, False), mk(out_ds, False)
     model = UNet(1, 1, 64).to(device)

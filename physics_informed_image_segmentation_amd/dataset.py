@@ -6,16 +6,21 @@ per-image min-max) — host-side, outside the kernel path.
 ``SyntheticDiscDataset`` is the benchmark/parity generator of SURVEY.md
 §8(c)-(d): per-sample union of random discs, noisy image, min-max;
 ``DeviceDiscLoader`` rasterises the same samples on the GPU (§8(f) row 1).
+``DeviceCachedLoader`` keeps any dataset, preprocessed once on the host
+(``pack_samples``), resident on the GPU and assembles every batch there
+(``pis_cache_batch``, csrc/cache.hip).
 """
 from __future__ import annotations
 
 import json
+import os
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
+from torch.utils.data import Dataset, Subset
 
 
 class CellSegmentationDataset(Dataset):
@@ -62,13 +67,21 @@ class CellSegmentationDataset(Dataset):
         canvas = canvas.resize(size, resample=Image.NEAREST)
         return (np.asarray(canvas, dtype=np.float32) > 0).astype(np.float32)
 
-    def __getitem__(self, idx):
+    def raw_item(self, idx):
+        """``(image_u8, mask_u8)``: the resized grey image as PIL returns it, (H, W) uint8, before
+        the min-max normalisation, and the binary mask as uint8 — what ``__getitem__`` is computed
+        from, and what the device cache stores (``pack_samples``). No ``transform`` is applied."""
         from PIL import Image
         image_id = self.image_ids[idx]
         info = self.images_dict[image_id]
         img = Image.open(self.image_dir / info["file_name"]).convert("L")
-        img = np.asarray(img.resize(self.image_size, resample=Image.BILINEAR), dtype=np.float32)
+        img = np.asarray(img.resize(self.image_size, resample=Image.BILINEAR), dtype=np.uint8)
         mask = self._mask(self.anns_by_image[image_id], (info["height"], info["width"]), self.image_size)
+        return img, mask.astype(np.uint8)
+
+    def __getitem__(self, idx):
+        img, mask = self.raw_item(idx)
+        img, mask = img.astype(np.float32), mask.astype(np.float32)
         img = (img - img.min()) / (img.max() - img.min() + 1e-8)
         image = torch.from_numpy(img).unsqueeze(0)
         mask_t = torch.from_numpy(mask).unsqueeze(0)
@@ -103,6 +116,24 @@ def _sample_generator(seed: int, idx: int) -> torch.Generator:
     return torch.Generator().manual_seed(seed * 1_000_003 + idx)
 
 
+def shard_indices(ids, shuffle: bool, seed: int, epoch: int, rank: int, world: int):
+    """This rank's sample ids for one epoch, as ``DistributedSampler(seed=seed)`` after
+    ``set_epoch(epoch)``: a ``torch.randperm`` seeded ``seed + epoch`` when ``shuffle``, padded to
+    a multiple of ``world`` by repeating its head, rank ``r`` taking every ``world``-th entry from
+    ``r``. Shared by ``DeviceDiscLoader`` and ``DeviceCachedLoader``."""
+    m = len(ids)
+    perm = (torch.randperm(m, generator=torch.Generator().manual_seed(seed + epoch)).tolist()
+            if shuffle else list(range(m)))
+    idx = [ids[k] for k in perm]
+    total = -(-m // world) * world
+    idx += idx[:total - len(idx)]
+    return idx[rank:total:world]
+
+
+def _num_batches(m: int, batch_size: int, drop_last: bool) -> int:
+    return m // batch_size if drop_last else -(-m // batch_size)
+
+
 class DeviceDiscLoader:
     """Batches of the disc generator rasterised ON THE GPU (``pis_synth_discs``,
     SURVEY §8(f) row 1): only the disc parameters (<= 14 x 3 floats per sample) cross
@@ -132,17 +163,10 @@ class DeviceDiscLoader:
         self.epoch = epoch
 
     def indices(self):
-        m = len(self.ids)
-        perm = (torch.randperm(m, generator=torch.Generator().manual_seed(self.seed + self.epoch)).tolist()
-                if self.shuffle else list(range(m)))
-        idx = [self.ids[k] for k in perm]
-        total = -(-m // self.world) * self.world
-        idx += idx[:total - len(idx)]
-        return idx[self.rank:total:self.world]
+        return shard_indices(self.ids, self.shuffle, self.seed, self.epoch, self.rank, self.world)
 
     def __len__(self):
-        m = len(self.indices())
-        return m // self.batch_size if self.drop_last else -(-m // self.batch_size)
+        return _num_batches(len(self.indices()), self.batch_size, self.drop_last)
 
     def _disc(self, i: int):
         p = self._params.get(i)
@@ -196,3 +220,277 @@ class SyntheticDiscDataset(Dataset):
     def __getitem__(self, idx):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + idx)
         return disc_sample(self.size[0], self.size[1], g)
+
+
+# ----------------------------------------------------------------------------
+# device-resident dataset cache
+# ----------------------------------------------------------------------------
+
+def _pad16(nbytes: int) -> int:
+    return -(-nbytes // 16) * 16
+
+
+def _unwrap(dataset, indices=None):
+    """The base dataset under any ``Subset`` wrappers and ``indices`` (default: all) mapped to it."""
+    idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    while isinstance(dataset, Subset):
+        sub = dataset.indices
+        idx = [int(sub[i]) for i in idx]
+        dataset = dataset.dataset
+    return dataset, idx
+
+
+def default_workers() -> int:
+    """Host threads for packing: at most 16, whatever the machine's CPU count says."""
+    return max(1, min(16, os.cpu_count() or 1))
+
+
+class PackedSamples(NamedTuple):
+    """Host arrays of a device cache (``pack_samples``). ``image`` and ``mask`` are (N, stride)
+    uint8 views of the rows, each row padded to a multiple of 16 bytes.
+
+    image_format "u8": H*W grey values per row, ``norm[i] = (lo, den)`` float32 with
+    ``den = float(hi - lo)`` if ``hi > lo`` else ``1e-8`` — what ``img.max() - img.min() + 1e-8``
+    rounds to in float32 — so ``(float(v) - lo) / den`` is the dataset item bit for bit;
+    "f32": the float image of ``__getitem__`` verbatim, ``norm`` is None.
+    mask_format "bits": ``np.packbits(mask, bitorder="little")``; "f32": verbatim."""
+    image: np.ndarray
+    mask: np.ndarray
+    norm: Optional[np.ndarray]
+    image_format: str
+    mask_format: str
+    size: Tuple[int, int]
+
+    @property
+    def nbytes(self) -> int:
+        return self.image.nbytes + self.mask.nbytes + (self.norm.nbytes if self.norm is not None else 0)
+
+    def __len__(self):
+        return self.image.shape[0]
+
+    def unpack(self, i: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Sample ``i`` as the (1, H, W) float32 pair the dataset returns (host reference of the kernel)."""
+        H, W = self.size
+        n = H * W
+        if self.image_format == "u8":
+            lo, den = self.norm[i]
+            img = (self.image[i, :n].astype(np.float32) - lo) / den
+        else:
+            img = self.image[i, :4 * n].view(np.float32).copy()
+        if self.mask_format == "bits":
+            mask = np.unpackbits(self.mask[i], bitorder="little")[:n].astype(np.float32)
+        else:
+            mask = self.mask[i, :4 * n].view(np.float32).copy()
+        return torch.from_numpy(img.reshape(1, H, W)), torch.from_numpy(mask.reshape(1, H, W))
+
+
+def _rows(rows, row_bytes: int) -> np.ndarray:
+    out = np.zeros((len(rows), _pad16(row_bytes)), np.uint8)
+    for k, r in enumerate(rows):
+        out[k, :row_bytes] = r
+    return out
+
+
+def pack_samples(dataset, indices=None, workers: Optional[int] = None) -> PackedSamples:
+    """Preprocess ``dataset[i]`` for ``i`` in ``indices`` (default: every sample) once, on at most
+    ``workers`` host threads (default ``min(16, os.cpu_count())``), into the arrays of a device
+    cache. Host only. ``dataset`` may be a ``torch.utils.data.Subset`` (what ``train_fraction``
+    produces): it is unwrapped through ``.dataset`` / ``.indices``.
+
+    A dataset with ``raw_item`` and no ``transform`` (``CellSegmentationDataset``) is stored as
+    uint8 pixels + a per-sample (lo, den) table; any other dataset (``SyntheticDiscDataset``, one
+    with a ``transform``, a user's own) as the float image ``__getitem__`` returns. A
+    ``transform`` is therefore evaluated ONCE, at cache time, and must be deterministic: a random
+    one would be frozen at its first draw (use the loader's ``augment`` instead). Masks are one
+    bit per pixel when every value of every mask is exactly 0 or 1, float32 otherwise."""
+    base, idx = _unwrap(dataset, indices)
+    if not idx:
+        raise ValueError("pack_samples: no samples")
+    u8 = hasattr(base, "raw_item") and getattr(base, "transform", None) is None
+
+    def one(i):
+        if u8:
+            img, mask = base.raw_item(i)
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            lo, hi = int(img.min()), int(img.max())
+            norm = (np.float32(lo), np.float32(hi - lo) if hi > lo else np.float32(1e-8))
+        else:
+            img, mask = base[i]
+            img = np.ascontiguousarray(torch.as_tensor(img).detach().cpu().numpy(), dtype=np.float32)
+            norm = None
+        mask = np.ascontiguousarray(torch.as_tensor(mask).detach().cpu().numpy())
+        hw = tuple(img.shape[-2:])
+        if img.ndim < 2 or img.size != hw[0] * hw[1] or mask.size != img.size:
+            raise ValueError(f"pack_samples: sample {i} is not one H x W channel (image {img.shape}, mask {mask.shape})")
+        binary = bool(np.all((mask == 0) | (mask == 1)))
+        flat = mask.reshape(-1)
+        packed = np.packbits(flat.astype(np.uint8), bitorder="little") if binary else flat.astype(np.float32).view(np.uint8)
+        return img.reshape(-1).view(np.uint8), norm, packed, binary, hw
+
+    n_workers = max(1, min(workers if workers is not None else default_workers(), len(idx)))
+    if n_workers == 1:
+        got = [one(i) for i in idx]
+    else:
+        with ThreadPoolExecutor(max_workers=n_workers) as pool:
+            got = list(pool.map(one, idx))
+    H, W = got[0][4]
+    if any(g[4] != (H, W) for g in got):
+        raise ValueError("pack_samples: samples differ in size")
+    n = H * W
+    bits = all(g[3] for g in got)
+    if bits:
+        mask_rows, mask_bytes = [g[2] for g in got], -(-n // 8)
+    else:  # a binary sample's bits unpack to its exact 0.0 / 1.0 values
+        mask_rows = [np.unpackbits(g[2], bitorder="little")[:n].astype(np.float32).view(np.uint8) if g[3] else g[2]
+                     for g in got]
+        mask_bytes = 4 * n
+    return PackedSamples(image=_rows([g[0] for g in got], n if u8 else 4 * n), mask=_rows(mask_rows, mask_bytes),
+                         norm=np.array([g[1] for g in got], np.float32).reshape(-1, 2) if u8 else None,
+                         image_format="u8" if u8 else "f32", mask_format="bits" if bits else "f32", size=(H, W))
+
+
+_AUGMENT_CODES = {None: 1, "flip": 4, "d4": 8}
+
+
+def apply_symmetry(t: torch.Tensor, s: int) -> torch.Tensor:
+    """Symmetry code ``s`` of ``pis_cache_batch`` on the last two dimensions: bit 0 flips W, bit 1
+    flips H, then bit 2 transposes."""
+    if s & 1:
+        t = t.flip(-1)
+    if s & 2:
+        t = t.flip(-2)
+    if s & 4:
+        t = t.transpose(-1, -2)
+    return t
+
+
+class DeviceCachedLoader:
+    """Batches of ANY map-style dataset assembled on the GPU from a device-resident cache.
+
+    Construction preprocesses the whole dataset once with its unchanged host code
+    (``pack_samples``: uint8 pixels + one bit per mask pixel for ``CellSegmentationDataset``, 36 KB
+    per 128^2 sample) and uploads it in pinned chunks; the cache arrays are plain torch tensors on
+    ``device``. EVERY RANK HOLDS THE FULL SET: the shards change with the epoch, so a rank needs any
+    sample sooner or later. If the packed set exceeds ``max_bytes`` (default: a quarter of the
+    device's free memory) a ``ValueError`` is raised before anything is allocated on the device.
+
+    The order is ``DeviceDiscLoader``'s and ``DistributedSampler(seed=seed)``'s (``shard_indices``;
+    ``set_epoch``, ``indices()``, ``len()``). At ``__iter__`` the epoch's index list and symmetry
+    codes go to the device in one copy; each batch is a slice of them and one ``pis_cache_batch``
+    launch on the current stream: no host work and no host-to-device copy per step. Batches are
+    ``(images, masks)`` of shape (b, 1, H, W) float32 on ``device``, bit-identical to
+    ``torch.stack`` of the dataset items, so ``train_epoch``, ``validate``, ``evaluate_model`` and
+    ``StepGraph.step`` take them as they are.
+
+    ``augment``: None (default), "flip" (codes 0-3: W and H flips) or "d4" (codes 0-7, adds the
+    transpose; square sizes only). Sample ``i``'s code in an epoch is entry ``i`` of one
+    ``torch.randint`` over the whole dataset from a generator seeded by (seed, epoch), so it does
+    not depend on ``world``, ``rank`` or ``batch_size`` (``symmetry_codes``). A dataset
+    ``transform`` is evaluated once, at cache time: it must be deterministic."""
+
+    CHUNK_BYTES = 64 << 20
+
+    def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 42, rank: int = 0, world: int = 1,
+                 drop_last: bool = False, device=None, workers: Optional[int] = None, max_bytes: Optional[int] = None,
+                 augment: Optional[str] = None):
+        from . import _hip  # noqa: F401  (fail early when the library is missing)
+        if augment not in _AUGMENT_CODES:
+            raise ValueError(f"augment must be None, 'flip' or 'd4', got {augment!r}")
+        self.dataset, self.batch_size, self.seed = dataset, batch_size, seed
+        self.shuffle, self.rank, self.world, self.drop_last = shuffle, rank, world, drop_last
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        self.augment = augment
+        self.epoch = 0
+        self.ids = list(range(len(dataset)))
+        packed = pack_samples(dataset, workers=workers)
+        self.size, self.image_format, self.mask_format = packed.size, packed.image_format, packed.mask_format
+        if augment == "d4" and self.size[0] != self.size[1]:
+            raise ValueError(f"augment='d4' transposes: it needs square samples, got {self.size[0]} x {self.size[1]}")
+        self.nbytes = packed.nbytes
+        limit = self.default_max_bytes(self.device) if max_bytes is None else int(max_bytes)
+        self.check_fits(self.nbytes, limit)
+        self.image = self._upload(packed.image)
+        self.mask = self._upload(packed.mask)
+        self.norm = self._upload(packed.norm) if packed.norm is not None else None
+
+    @staticmethod
+    def default_max_bytes(device) -> Optional[int]:
+        """A quarter of the device's free memory (None = no limit for a host 'device')."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            return None
+        return torch.cuda.mem_get_info(device)[0] // 4
+
+    @staticmethod
+    def check_fits(nbytes: int, max_bytes: Optional[int]) -> None:
+        if max_bytes is not None and nbytes > max_bytes:
+            raise ValueError(f"DeviceCachedLoader: the packed dataset takes {nbytes} bytes, more than "
+                             f"max_bytes = {max_bytes}")
+
+    def _upload(self, arr: np.ndarray) -> torch.Tensor:
+        src = torch.from_numpy(arr)
+        if self.device.type != "cuda":
+            return src.clone()
+        dst = torch.empty(src.shape, dtype=src.dtype, device=self.device)
+        if src.numel() == 0:
+            return dst
+        row = src[0].numel() * src.element_size()
+        step = max(1, self.CHUNK_BYTES // row)
+        pinned = torch.empty((min(step, src.shape[0]),) + tuple(src.shape[1:]), dtype=src.dtype, pin_memory=True)
+        for k in range(0, src.shape[0], step):
+            part = src[k:k + step]
+            pinned[:part.shape[0]].copy_(part)
+            dst[k:k + step].copy_(pinned[:part.shape[0]], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()  # the staging buffer is reused
+        return dst
+
+    def set_epoch(self, epoch: int):
+        self.epoch = epoch
+
+    def indices(self):
+        return shard_indices(self.ids, self.shuffle, self.seed, self.epoch, self.rank, self.world)
+
+    def __len__(self):
+        return _num_batches(len(self.indices()), self.batch_size, self.drop_last)
+
+    def symmetry_codes(self, epoch: Optional[int] = None) -> torch.Tensor:
+        """uint8 code of every dataset sample (dataset-index order) in ``epoch`` (default: the
+        current one); all zero without ``augment``."""
+        n = len(self.ids)
+        k = _AUGMENT_CODES[self.augment]
+        if k == 1:
+            return torch.zeros(n, dtype=torch.uint8)
+        e = self.epoch if epoch is None else epoch
+        g = torch.Generator().manual_seed(self.seed * 1_000_003 + e)
+        return torch.randint(0, k, (n,), generator=g, dtype=torch.uint8)
+
+    def __iter__(self):
+        from . import _hip
+        _hip.require_cuda(self.image, "DeviceCachedLoader")
+        idx = self.indices()
+        m = len(idx)
+        stop = m - (m % self.batch_size if self.drop_last else 0)
+        # one host-to-device copy per epoch: the int64 index list, then one symmetry byte per entry
+        plan = torch.empty(8 * m + (m if self.augment else 0), dtype=torch.uint8, pin_memory=True)
+        ids = torch.tensor(idx, dtype=torch.int64)
+        plan[:8 * m].view(torch.int64).copy_(ids)
+        if self.augment:
+            plan[8 * m:].copy_(self.symmetry_codes()[ids])
+        plan_d = plan.to(self.device, non_blocking=True)
+        return self._batches(plan_d, m, stop)
+
+    def _batches(self, plan_d: torch.Tensor, m: int, stop: int):
+        from . import _hip
+        H, W = self.size
+        img_fmt = _hip.PIS_CACHE_IMG_U8 if self.image_format == "u8" else _hip.PIS_CACHE_IMG_F32
+        mask_fmt = _hip.PIS_CACHE_MASK_BITS if self.mask_format == "bits" else _hip.PIS_CACHE_MASK_F32
+        idx_p, sym_p = plan_d.data_ptr(), (plan_d.data_ptr() + 8 * m if self.augment else 0)
+        n, bs = self.image.shape[0], self.batch_size
+        for k in range(0, stop, bs):
+            b = min(bs, m - k)
+            img = torch.empty(b, 1, H, W, device=self.device)
+            mask = torch.empty(b, 1, H, W, device=self.device)
+            _hip.call("pis_cache_batch", self.image.data_ptr(), img_fmt, self.image.stride(0), self.mask.data_ptr(),
+                      mask_fmt, self.mask.stride(0), _hip.ptr(self.norm), idx_p + 8 * k, sym_p + k if sym_p else 0,
+                      n, img.data_ptr(), mask.data_ptr(), b, H, W, _hip.stream_handle(self.device))
+            yield img, mask

@@ -317,16 +317,28 @@ def format_metric_report(metrics: Dict[str, np.ndarray], model_name: str = "Mode
 
 
 def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8, threshold: float = 0.5,
-                         model_name: str = "Model") -> Dict[str, np.ndarray]:
-    """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522)."""
+                         model_name: str = "Model", device_cache: bool = False) -> Dict[str, np.ndarray]:
+    """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
+    ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
+    (``dataset.DeviceCachedLoader``) instead of ``DataLoader`` workers; a set that does not fit
+    falls back to them."""
     from torch.utils.data import DataLoader
 
-    from .dataset import CellSegmentationDataset
+    from .dataset import CellSegmentationDataset, DeviceCachedLoader
     print(f"\nEvaluating {model_name} on test set...")
     print("=" * 70)
     ds = CellSegmentationDataset(test_dir, test_json)
-    loader = DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=2,
-                        pin_memory=torch.cuda.is_available())
+    loader = None
+    if device_cache:
+        try:
+            loader = DeviceCachedLoader(ds, batch_size, shuffle=False, device=device)
+        except ValueError as e:
+            if "max_bytes" not in str(e):
+                raise
+            print(f"device cache not used, falling back to DataLoader workers: {e}")
+    if loader is None:
+        loader = DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=2,
+                            pin_memory=torch.cuda.is_available())
     print(f"Test samples: {len(ds)}")
     metrics = evaluate_model(model, loader, device, threshold=threshold)
     print(format_metric_report(metrics, model_name=model_name))

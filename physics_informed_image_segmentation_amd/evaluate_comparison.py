@@ -73,16 +73,18 @@ def _print_comparison(results: Dict[str, Dict[str, float]]):
 
 def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_dir: Path, test_json: Path,
                          device: torch.device, batch_size: int = 8, threshold: float = 0.5,
-                         output_dir: Optional[Path] = None) -> Dict:
+                         output_dir: Optional[Path] = None, device_cache: bool = False) -> Dict:
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
     print("=" * 70 + "\nMODEL EVALUATION AND STATISTICAL COMPARISON\n" + "=" * 70)
     print("\nLoading models...")
     base = evaluate_on_test_set(load_model(baseline_model_path, device), test_dir, test_json, device,
-                                batch_size=batch_size, threshold=threshold, model_name="Baseline (Unconstrained)")
+                                batch_size=batch_size, threshold=threshold, model_name="Baseline (Unconstrained)",
+                                device_cache=device_cache)
     pde = evaluate_on_test_set(load_model(pde_model_path, device), test_dir, test_json, device,
-                               batch_size=batch_size, threshold=threshold, model_name="PDE-Constrained")
+                               batch_size=batch_size, threshold=threshold, model_name="PDE-Constrained",
+                               device_cache=device_cache)
     print("\n" + "=" * 70 + "\nSTATISTICAL COMPARISON\n" + "=" * 70)
     cmp = compare_models_statistically(base, pde, alpha=0.05)
     _print_comparison(cmp)
@@ -117,7 +119,7 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
 
 def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: List[Path], test_dir: Path,
                              test_json: Path, device: torch.device, batch_size: int = 8, threshold: float = 0.5,
-                             output_dir: Optional[Path] = None) -> Dict:
+                             output_dir: Optional[Path] = None, device_cache: bool = False) -> Dict:
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -128,7 +130,7 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
         print(f"\n{'=' * 70}\nRun {i + 1}/{len(baseline_model_paths)}\n{'=' * 70}")
         for tag, path, label in (("baseline", bp, f"Baseline Run {i + 1}"), ("pde", pp, f"PDE-Constrained Run {i + 1}")):
             m = evaluate_on_test_set(load_model(path, device), test_dir, test_json, device, batch_size=batch_size,
-                                     threshold=threshold, model_name=label)
+                                     threshold=threshold, model_name=label, device_cache=device_cache)
             for k in METRIC_KEYS:
                 pooled[tag][k].extend(m[k])
     base = {k: np.array(v) for k, v in pooled["baseline"].items()}

@@ -32,7 +32,7 @@ import torch
 from torch.utils.data import DataLoader, Subset
 
 from . import _hip
-from .dataset import CellSegmentationDataset, DeviceDiscLoader, SyntheticDiscDataset
+from .dataset import CellSegmentationDataset, DeviceCachedLoader, DeviceDiscLoader, SyntheticDiscDataset
 from .distributed import GradBucketer, allreduce_scalars, broadcast_parameters, init_from_env
 from .fused import LossConfig, loss_forward
 from .loss import DiceBCELoss, DiceBCEPDELoss
@@ -446,6 +446,23 @@ def _loaders(train_ds, val_ds, batch_size: int, world: int, rank: int, workers: 
             DataLoader(val_ds, batch_size=batch_size, shuffle=False, num_workers=workers, pin_memory=pin))
 
 
+def _cached_loaders(train_ds, val_ds, batch_size: int, world: int, rank: int, device, seed: int,
+                    augment: Optional[str], say=print):
+    """``device_cache=True``: both sets resident on the GPU, batches assembled there
+    (``DeviceCachedLoader``; ``augment`` on the training loader only). None when a set does not
+    fit (said, and the caller falls back to the ``DataLoader`` path)."""
+    try:
+        return (DeviceCachedLoader(train_ds, batch_size, shuffle=True, seed=seed, rank=rank, world=world,
+                                   device=device, augment=augment),
+                DeviceCachedLoader(val_ds, batch_size, shuffle=False, seed=seed, rank=rank, world=world,
+                                   device=device))
+    except ValueError as e:
+        if "max_bytes" not in str(e):
+            raise
+        say(f"device cache not used, falling back to DataLoader workers: {e}")
+        return None
+
+
 _REPO_ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -454,7 +471,8 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           batch_size: int = 8, learning_rate: float = 1e-4, stage1_epochs: int = 50, stage2_epochs: int = 50,
           early_stopping_patience: int = 10, train_fraction: Optional[float] = None, seed: int = 42,
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
-          num_workers: int = 2, device_data: bool = True):
+          num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
+          augment: Optional[str] = None):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -467,7 +485,13 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     the repository root, like the reference's ``Path(__file__).parent.parent``),
     ``synthetic=(n_train, n_val, H, W)`` to train on the SURVEY §8(c) disc generator when the
     cell dataset is not present — rasterised on the GPU (``DeviceDiscLoader``, sharded like
-    DistributedSampler) unless ``device_data=False``."""
+    DistributedSampler) unless ``device_data=False``; ``device_cache=True`` to preprocess the
+    datasets once on the host and serve every batch from a device-resident cache
+    (``DeviceCachedLoader``: the cell dataset, a ``train_fraction`` subset, or the disc dataset with
+    ``device_data=False``), with ``augment`` ("flip" / "d4") on its training loader; a cache that
+    does not fit falls back to the ``DataLoader`` path."""
+    if augment is not None and not device_cache:
+        raise ValueError("augment needs device_cache=True (the symmetries are applied by the cache kernel)")
     rank, local_rank, world = init_from_env()
     if not torch.cuda.is_available():
         raise _hip.HipError("train(): the MI355X path needs a GPU (no CPU fallback in this build)")
@@ -503,13 +527,17 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         train_ds = create_subset_dataset(train_ds, train_fraction)
     frac = f"_frac{train_fraction:.2f}" if train_fraction is not None else ""
     if synthetic is not None and device_data:
+        if augment is not None:
+            raise ValueError("augment applies to the device cache: pass device_data=False with synthetic data")
         subset = train_ds.indices if isinstance(train_ds, Subset) else None
         train_loader = DeviceDiscLoader(n_tr, batch_size, (H, W), seed=seed, shuffle=True, rank=rank, world=world,
                                         device=device, subset=subset)
         val_loader = DeviceDiscLoader(n_va, batch_size, (H, W), seed=seed + 1, shuffle=False, rank=rank,
                                       world=world, device=device)
     else:
-        train_loader, val_loader = _loaders(train_ds, val_ds, batch_size, world, rank, num_workers)
+        cached = _cached_loaders(train_ds, val_ds, batch_size, world, rank, device, seed, augment, say) \
+            if device_cache else None
+        train_loader, val_loader = cached or _loaders(train_ds, val_ds, batch_size, world, rank, num_workers)
     say(f"Training samples: {len(train_ds)}")
     say(f"Validation samples: {len(val_ds)}")
     say(f"Batch size: {batch_size} per GPU")
@@ -596,7 +624,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         from .evaluate import evaluate_on_test_set
         name = "PDE-Constrained (Stage II)" if use_two_stage else "Single-Stage PDE-Constrained"
         m = evaluate_on_test_set(model, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
-                                 model_name=name)
+                                 model_name=name, device_cache=device_cache)
         tag = "stage2" if use_two_stage else "single_stage"
         save_test_metrics(m, out_dir / f"test_metrics_{tag}_{stamp}{frac}", model_name=name)
         result["test"] = m
@@ -606,7 +634,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
             stage1.load_state_dict(torch.load(stage1_path, map_location="cpu", weights_only=True))
             stage1 = stage1.to(device)
             m1 = evaluate_on_test_set(stage1, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
-                                      model_name="Baseline (Stage I)")
+                                      model_name="Baseline (Stage I)", device_cache=device_cache)
             save_test_metrics(m1, out_dir / f"test_metrics_stage1_{stamp}{frac}", model_name="Baseline (Stage I)")
             result["test_stage1"] = m1
     elif is_main:

@@ -38,7 +38,13 @@ def main(argv=None):
                     help="train/evaluate on the seeded disc generator instead of the image folders")
     ap.add_argument("--no-boundary-metrics", action="store_true")
     ap.add_argument("--num-workers", type=int, default=2)
+    ap.add_argument("--device-cache", action="store_true",
+                    help="preprocess the datasets once and serve every batch from a device-resident cache")
+    ap.add_argument("--augment", choices=["flip", "d4"], default=None,
+                    help="random flips / all 8 grid symmetries on the training loader (needs --device-cache)")
     args = ap.parse_args(argv)
+    if args.augment and not args.device_cache:
+        ap.error("--augment needs --device-cache")
     if not torch.cuda.is_available():
         raise SystemExit("run_ablation.py: the MI355X path needs a GPU (no CPU fallback in this build)")
     device = torch.device("cuda")
@@ -59,7 +65,8 @@ def main(argv=None):
                                  stage2_epochs=args.stage2_epochs,
                                  early_stopping_patience=args.early_stopping_patience,
                                  output_dir=Path(args.output_dir) if args.output_dir else None,
-                                 num_workers=args.num_workers, boundary_metrics=not args.no_boundary_metrics)
+                                 num_workers=args.num_workers, boundary_metrics=not args.no_boundary_metrics,
+                                 device_cache=args.device_cache, augment=args.augment)
         print(f"\nAblation {name} complete!\nResults: {res['results_json']}\nSummary: {res['summary_csv']}")
         out[name] = res
     print("\n" + "=" * 70 + "\nALL ABLATION STUDIES COMPLETE\n" + "=" * 70)

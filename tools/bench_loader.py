@@ -1,0 +1,213 @@
+"""The device-resident dataset cache against the loaders it replaces, at 8 x 512^2 and 64 x 128^2.
+
+    python tools/bench_loader.py                    # both parts, both sizes -> profiles/device_cache.txt
+    python tools/bench_loader.py --part a --out -   # kernel only, to stdout
+
+The dataset is a COCO-style folder the tool writes into a temporary directory (--images grey
+PNGs with a few polygon annotations each), read through the unchanged ``CellSegmentationDataset``.
+
+(a) ``pis_cache_batch`` per launch, timed with HIP events, median of --reps: cold (a 1 GiB read
+between launches, bench.py's protocol, so cache rows and outputs start outside the Infinity Cache)
+and warm (back to back). Beside it ONE ``pis_debug_stream_probe`` launch (dst = a + b) over as
+many floats as make its 12 B per element equal the cache kernel's algorithmic bytes (the cache
+rows, norm and index entries it reads, the two fp32 batches it writes), same protocol, best over
+the probe's grid sizes. The issue's bar: kernel <= 1.5 x probe at both sizes.
+
+(b) ``train_epoch`` (C2 model, Stage-II loss, default metrics) images/s over four loaders that
+alternate in one process, after one warm-up epoch each: the cached loader, a list of the same
+batches already resident on the device, ``DataLoader`` with 2 and with 16 workers (spawned once,
+``persistent_workers``, so their start-up is not in the timed epochs and they hold no GPU).
+``train_epoch`` ends in its host synchronisation: a host clock around it is the epoch time. The
+bar: cached >= 0.97 x resident list. The DataLoader rows are for the record.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SIZES = [(8, 512, 512), (64, 128, 128)]
+
+
+def write_dataset(root: Path, n: int, seed: int = 0):
+    """n grey images (192 x 256, smooth blobs + noise, each with its own grey range) and 2-4 polygon
+    annotations per image."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    img_dir = root / "images"
+    img_dir.mkdir(parents=True)
+    SH, SW = 192, 256
+    yy, xx = np.mgrid[0:SH, 0:SW]
+    imgs, anns = [], []
+    for i in range(n):
+        lo, hi = int(rng.integers(0, 80)), int(rng.integers(150, 256))
+        field = np.zeros((SH, SW))
+        segs = []
+        for _ in range(int(rng.integers(2, 5))):
+            cx, cy, r = rng.uniform(30, SW - 30), rng.uniform(30, SH - 30), rng.uniform(12, 28)
+            field += np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * r * r))
+            th = np.linspace(0, 2 * np.pi, 12, endpoint=False)
+            rad = r * rng.uniform(0.8, 1.2, th.size)
+            segs.append(np.stack([cx + rad * np.cos(th), cy + rad * np.sin(th)], 1).round(1).reshape(-1).tolist())
+        a = lo + (hi - lo) * np.clip(field + 0.05 * rng.standard_normal((SH, SW)), 0, 1)
+        Image.fromarray(a.astype(np.uint8), mode="L").save(img_dir / f"{i:04d}.png")
+        imgs.append({"id": i, "file_name": f"{i:04d}.png", "height": SH, "width": SW})
+        anns.append({"id": i, "image_id": i, "segmentation": segs})
+    ann = root / "ann.json"
+    ann.write_text(json.dumps({"images": imgs, "annotations": anns}))
+    return img_dir, ann
+
+
+def event_ms(fn, reps, flush=None, sink=None):
+    evs = []
+    for _ in range(reps + 3):
+        if flush is not None:
+            torch.sum(flush, dim=0, out=sink)  # a READ: evicts with clean lines (no write-back tail)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        evs.append((e0, e1))
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in evs[3:])
+
+
+def part_a(ds_at, reps, say):
+    from physics_informed_image_segmentation_amd import _hip
+    from physics_informed_image_segmentation_amd.dataset import DeviceCachedLoader
+    lib = _hip.lib()
+    st = _hip.stream_handle()
+    flush = torch.ones(256 << 20, device="cuda")  # 1 GiB
+    sink = torch.empty((), device="cuda")
+    say("(a) pis_cache_batch per launch vs one pis_debug_stream_probe launch over the same bytes "
+        f"(HIP events, median of {reps})")
+    ok = True
+    for B, H, W in SIZES:
+        ld = DeviceCachedLoader(ds_at(H, W), B, shuffle=True, seed=1)
+        n = ld.image.shape[0]
+        idx = torch.tensor(ld.indices()[:B], dtype=torch.int64).cuda()
+        img = torch.empty(B, 1, H, W, device="cuda")
+        mask = torch.empty_like(img)
+        args = (ld.image.data_ptr(), _hip.PIS_CACHE_IMG_U8, ld.image.stride(0), ld.mask.data_ptr(),
+                _hip.PIS_CACHE_MASK_BITS, ld.mask.stride(0), ld.norm.data_ptr(), idx.data_ptr(), 0, n, img.data_ptr(),
+                mask.data_ptr(), B, H, W, st)
+
+        def kernel():
+            if lib.pis_cache_batch(*args) != 0:
+                raise RuntimeError(lib.pis_last_error().decode())
+        assert (ld.image_format, ld.mask_format) == ("u8", "bits")
+        nbytes = B * (H * W + -(-H * W // 8) + 8 + 8) + 2 * B * H * W * 4
+        nf = -(-nbytes // 48) * 4  # floats per probe array: 12 B per element, n % 4 == 0
+        a, b, dst = (torch.ones(nf, device="cuda") for _ in range(3))
+
+        def probe(grid):
+            if lib.pis_debug_stream_probe(a.data_ptr(), b.data_ptr(), dst.data_ptr(), nf, 0, grid, st) != 0:
+                raise RuntimeError(lib.pis_last_error().decode())
+        for state, fl in (("cold", flush), ("warm", None)):
+            k_ms = event_ms(kernel, reps, fl, sink)
+            p_ms, grid = min((event_ms(lambda g=g: probe(g), reps, fl, sink), g) for g in (256, 512, 1024, 2048, 4096))
+            ratio = k_ms / p_ms
+            ok &= ratio <= 1.5
+            say(f"  {B:3d} x {H}^2  {state}:  cache_batch {k_ms * 1e3:8.2f} us ({nbytes / k_ms / 1e6:7.1f} GB/s)   "
+                f"probe {p_ms * 1e3:8.2f} us (grid {grid}, {12 * nf} B)   ratio {ratio:.2f}   "
+                f"[{nbytes} algorithmic bytes, cache {ld.nbytes} B for {n} samples]")
+    say(f"  bar: ratio <= 1.5 at both sizes, in both cache states: {'MET' if ok else 'MISSED'}")
+    return ok
+
+
+def part_b(ds_at, rounds, say):
+    from torch.utils.data import DataLoader
+
+    from physics_informed_image_segmentation_amd import AdamW, DiceBCEPDELoss, UNet
+    from physics_informed_image_segmentation_amd.dataset import DeviceCachedLoader
+    from physics_informed_image_segmentation_amd.train import train_epoch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    say(f"(b) train_epoch images/s, loaders alternating in one process, 1 warm-up + {rounds} timed epochs each")
+    ok = True
+    for B, H, W in SIZES:
+        ds = ds_at(H, W)
+        torch.manual_seed(42)
+        net = UNet(1, 1, 64).to(dev)
+        crit = DiceBCEPDELoss(pde_weight=1e-4, phase_field_weight=1e-4, diffusion_coeff=5.0, reaction_threshold=0.5,
+                              epsilon=0.05).to(dev)
+        opt = AdamW(net.parameters(), lr=1e-5, weight_decay=1e-5)
+        t0 = time.perf_counter()
+        cached = DeviceCachedLoader(ds, B, shuffle=True, seed=1)
+        torch.cuda.synchronize()
+        t_pack = time.perf_counter() - t0
+        resident = list(cached)
+        mk = lambda w: DataLoader(ds, batch_size=B, shuffle=True, num_workers=w, pin_memory=True,
+                                  persistent_workers=True, multiprocessing_context="spawn")
+        loaders = {"cached loader": cached, "resident batch list": resident, "DataLoader, 2 workers": mk(2),
+                   "DataLoader, 16 workers": mk(16)}
+        times = {k: [] for k in loaders}
+        for r in range(rounds + 1):
+            for name, ld in loaders.items():
+                if hasattr(ld, "set_epoch"):
+                    ld.set_epoch(r)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                train_epoch(net, ld, crit, opt, dev, return_components=True)
+                torch.cuda.synchronize()
+                if r:
+                    times[name].append(time.perf_counter() - t0)
+        n = len(ds)
+        say(f"  {B:3d} x {H}^2, {n} images per epoch (cache built once in {t_pack:.2f} s: {cached.nbytes} B)")
+        rate = {}
+        for name, ts in times.items():
+            rate[name] = n / statistics.median(ts)
+            say(f"    {name:24s} {rate[name]:9.1f} images/s   (epochs: " + ", ".join(f"{t:.3f}" for t in ts) + " s)")
+        frac = rate["cached loader"] / rate["resident batch list"]
+        ok &= frac >= 0.97
+        say(f"    cached / resident = {frac:.3f}   cached / DataLoader(2) = "
+            f"{rate['cached loader'] / rate['DataLoader, 2 workers']:.2f}   cached / DataLoader(16) = "
+            f"{rate['cached loader'] / rate['DataLoader, 16 workers']:.2f}")
+        ld = None
+        del loaders, resident, cached, mk  # the DataLoaders' persistent workers stop with them
+    say(f"  bar: cached >= 0.97 x resident at both sizes: {'MET' if ok else 'MISSED'}")
+    return ok
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--part", choices=["a", "b", "all"], default="all")
+    ap.add_argument("--images", type=int, default=256, help="images in the generated dataset")
+    ap.add_argument("--reps", type=int, default=50, help="timed launches per kernel figure")
+    ap.add_argument("--rounds", type=int, default=3, help="timed epochs per loader")
+    ap.add_argument("--out", default=str(Path(__file__).resolve().parent.parent / "profiles" / "device_cache.txt"),
+                    help="report file ('-': stdout only)")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_loader.py: needs the MI355X (no CPU fallback)")
+    from physics_informed_image_segmentation_amd.dataset import CellSegmentationDataset
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    say(f"tools/bench_loader.py --images {args.images} --reps {args.reps} --rounds {args.rounds}   "
+        f"[{torch.cuda.get_device_name(0)}, torch {torch.__version__}]")
+    with tempfile.TemporaryDirectory() as tmp:
+        img_dir, ann = write_dataset(Path(tmp), args.images)
+        ds_at = lambda H, W: CellSegmentationDataset(img_dir, ann, image_size=(W, H))
+        ok = True
+        if args.part in ("a", "all"):
+            ok &= part_a(ds_at, args.reps, say)
+        if args.part in ("b", "all"):
+            ok &= part_b(ds_at, args.rounds, say)
+    if args.out != "-":
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
