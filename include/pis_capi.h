@@ -380,7 +380,9 @@ int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float
  * H, W are the INPUT resolution. y is contiguous (ld = C).
  * bwd (fused with the skip-gradient sum and the ReLU backward of the pooled
  * block's output):  dx[p][c] = (dskip[p][c] + [p = argmax] dy[q][c]) * (x[p][c] > 0)
- * dskip may be NULL; dx has ld = lddx.                                            */
+ * dskip may be NULL; dx has ld = lddx.
+ * C and every ld are multiples of 4, every ld >= C, and x, y, dy, dskip, dx are 16-byte aligned
+ * (float4 accesses); anything else is PIS_ERR_ARG.                                  */
 int pis_maxpool2x2_fwd(const float* x, int ldx, float* y, int B, int H, int W, int C,
                        pis_stream_t stream);
 int pis_maxpool2x2_bwd(const float* x, int ldx, const float* dy, const float* dskip, int ldskip,
@@ -390,7 +392,11 @@ int pis_maxpool2x2_bwd(const float* x, int ldx, const float* dy, const float* ds
  * fwd: z[p] = b + sum_c x[p][c] w[c];  u[p] = 1 / (1 + exp(-z[p]))
  * bwd: d[p] = g[p] * u[p] (1 - u[p]) when u != NULL (sigmoid backward), else g[p];
  *      dx[p][c] = d[p] w[c] (x[p][c] > 0)  (ReLU backward of dec1 fused);
- *      dw[c] (+)= sum_p d[p] x[p][c];  db (+)= sum_p d[p]                         */
+ *      dw[c] (+)= sum_p d[p] x[p][c];  db (+)= sum_p d[p]
+ * fwd's z and bwd's u and db may be NULL. C % 4 == 0 (bwd: C <= 1024), ldx and lddx multiples of 4
+ * and >= C, x, w, dx and ws 16-byte aligned (g, u, z, b, dw, db need none); ws holds at least
+ * pis_head_bwd_ws(npix, C) bytes. Anything else is PIS_ERR_ARG; pis_head_bwd_ws answers 0 (and
+ * sets pis_last_error) for sizes pis_head_bwd refuses.                              */
 int pis_head_fwd(const float* x, int ldx, const float* w, const float* b, float* z, float* u,
                  int64_t npix, int C, pis_stream_t stream);
 size_t pis_head_bwd_ws(int64_t npix, int C);
@@ -471,7 +477,10 @@ int pis_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, doub
                    double beta2, double eps, double weight_decay, double step_size, double bc2_sqrt,
                    double grad_scale, pis_stream_t stream);
 
-/* ---- channel sums (bias gradients): out[c] (+)= sum_p src[p*ld + c] ---- */
+/* ---- channel sums (bias gradients): out[c] (+)= sum_p src[p*ld + c] ----
+ * ld >= C; ws holds at least pis_colsum_ws(npix, C) bytes. When C % 4 == 0, ld % 4 == 0 and src
+ * and ws are 16-byte aligned (float4 loads); any other C, and out always, needs no alignment.
+ * Anything else is PIS_ERR_ARG. */
 size_t pis_colsum_ws(int64_t npix, int C);
 int pis_colsum(const float* src, int ld, int64_t npix, int C, float* out, int flags, void* ws,
                size_t ws_bytes, pis_stream_t stream);

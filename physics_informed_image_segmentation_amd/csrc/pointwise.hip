@@ -286,11 +286,18 @@ using namespace pis;
 
 static int grid_for(int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, 256), 8192)); }
 
+// the float4 kernels read and write 16-byte vectors at base + 4 * (multiple of 4) floats
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16 == 0;
+}
+
 extern "C" int pis_maxpool2x2_fwd(const float* x, int ldx, float* y, int B, int H, int W, int C,
                                   pis_stream_t stream) {
   PIS_CHECK_ARG(x && y && B > 0 && H >= 2 && W >= 2 && C > 0, "pis_maxpool2x2_fwd: bad arguments");
   PIS_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && ldx % 4 == 0,
                 "pis_maxpool2x2_fwd: H, W even and C, ldx multiples of 4 required");
+  PIS_CHECK_ARG(ldx >= C, "pis_maxpool2x2_fwd: ldx must be at least C");
+  PIS_CHECK_ARG(aligned16(x, y), "pis_maxpool2x2_fwd: buffers must be 16-byte aligned");
   const int64_t work = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream,
                      x, ldx, y, B, H / 2, W / 2, C);
@@ -304,6 +311,9 @@ extern "C" int pis_maxpool2x2_bwd(const float* x, int ldx, const float* dy, cons
   PIS_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 &&
                     (!dskip || ldskip % 4 == 0),
                 "pis_maxpool2x2_bwd: H, W even and C, ld multiples of 4 required");
+  PIS_CHECK_ARG(ldx >= C && lddx >= C && (!dskip || ldskip >= C),
+                "pis_maxpool2x2_bwd: ldx, lddx and ldskip must be at least C");
+  PIS_CHECK_ARG(aligned16(x, dy, dskip, dx), "pis_maxpool2x2_bwd: buffers must be 16-byte aligned");
   const int64_t work = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
   if (work < (int64_t)1 << 30)
     hipLaunchKernelGGL(maxpool_bwd_kernel<int>, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream,
@@ -318,6 +328,8 @@ extern "C" int pis_head_fwd(const float* x, int ldx, const float* w, const float
                             float* u, int64_t npix, int C, pis_stream_t stream) {
   PIS_CHECK_ARG(x && w && b && u && npix > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0,
                 "pis_head_fwd: bad arguments");
+  PIS_CHECK_ARG(ldx >= C, "pis_head_fwd: ldx must be at least C");
+  PIS_CHECK_ARG(aligned16(x, w), "pis_head_fwd: x and w must be 16-byte aligned");
   if (C == 64) {  // 4 pixels per 16-lane group
     hipLaunchKernelGGL(head_fwd64_kernel<4>, dim3((unsigned)cdiv(cdiv(npix, 4) * 16, 256)), dim3(256), 0,
                        (hipStream_t)stream, x, ldx, w, b, z, u, npix);
@@ -329,6 +341,10 @@ extern "C" int pis_head_fwd(const float* x, int ldx, const float* w, const float
 }
 
 extern "C" size_t pis_head_bwd_ws(int64_t npix, int C) {
+  if (!(npix > 0 && C > 0 && C % 4 == 0 && C / 4 <= 256)) {  // a size query has no error code: 0 bytes
+    set_error("pis_head_bwd_ws: npix > 0 and C a multiple of 4 in 4..1024 required");
+    return 0;
+  }
   const int64_t blocks = cdiv(npix, head_pix_per_block(npix));
   return (size_t)blocks * (C + 1) * sizeof(float) + 256;
 }
@@ -336,10 +352,12 @@ extern "C" size_t pis_head_bwd_ws(int64_t npix, int C) {
 extern "C" int pis_head_bwd(const float* x, int ldx, const float* w, const float* g, const float* u,
                             float* dx, int lddx, float* dw, float* db, int64_t npix, int C,
                             int flags, void* ws, size_t ws_bytes, pis_stream_t stream) {
-  PIS_CHECK_ARG(x && w && g && dx && dw && npix > 0 && C % 4 == 0 && C / 4 <= 256 &&
+  PIS_CHECK_ARG(x && w && g && dx && dw && npix > 0 && C > 0 && C % 4 == 0 && C / 4 <= 256 &&
                     ldx % 4 == 0 && lddx % 4 == 0,
                 "pis_head_bwd: bad arguments");
-  PIS_CHECK_ARG(ws_bytes >= pis_head_bwd_ws(npix, C), "pis_head_bwd: workspace too small");
+  PIS_CHECK_ARG(ldx >= C && lddx >= C, "pis_head_bwd: ldx and lddx must be at least C");
+  PIS_CHECK_ARG(aligned16(x, w, dx, ws), "pis_head_bwd: x, w, dx and ws must be 16-byte aligned");
+  PIS_CHECK_ARG(ws && ws_bytes >= pis_head_bwd_ws(npix, C), "pis_head_bwd: workspace missing or too small");
   hipStream_t s = (hipStream_t)stream;
   const int acc = flags & PIS_ACCUMULATE;
   const int64_t ppb = head_pix_per_block(npix);

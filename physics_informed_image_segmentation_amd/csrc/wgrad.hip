@@ -1362,6 +1362,12 @@ extern "C" int pis_colsum(const float* src, int ld, int64_t npix, int C, float* 
                           void* ws, size_t ws_bytes, pis_stream_t stream) {
   PIS_CHECK_ARG(src && out && npix > 0 && C > 0, "pis_colsum: bad arguments");
   PIS_CHECK_ARG(C % 4 != 0 || ld % 4 == 0, "pis_colsum: ld must be a multiple of 4");
+  PIS_CHECK_ARG(ld >= C, "pis_colsum: ld must be at least C");
+  PIS_CHECK_ARG(ws && ws_bytes >= colsum_ws(npix, C), "pis_colsum: workspace missing or too small");
+  // float4 loads of src and float4 stores of the partial slabs; a scalar C (and any out) has no
+  // alignment to keep: the slab reduction falls back to scalar columns on its own
+  PIS_CHECK_ARG(C % 4 != 0 || ((uintptr_t)src | (uintptr_t)ws) % 16 == 0,
+                "pis_colsum: src and ws must be 16-byte aligned when C is a multiple of 4");
   return colsum(src, ld, npix, C, out, flags & PIS_ACCUMULATE, ws, ws_bytes, (hipStream_t)stream);
 }
 
