@@ -32,7 +32,7 @@ def parse_args(argv=None):
                     help="Run repeated experiments evaluation (baseline and pde should be glob patterns)")
     ap.add_argument("--device-cache", action="store_true",
                     help="preprocess the test set once and serve every batch from a device-resident cache")
-    ap.add_argument("--augment", choices=["flip", "d4"], default=None,
+    ap.add_argument("--augment", choices=["flip", "d4", "affine"], default=None,
                     help="accepted so main.py's data flags can be passed unchanged; it applies to training "
                          "loaders only, and evaluation has none")
     return ap.parse_args(argv)

@@ -542,6 +542,31 @@ int pis_cache_batch(const void* img, int img_fmt, size_t img_stride, const void*
                     size_t mask_stride, const float* norm, const int64_t* idx, const uint8_t* sym, int64_t N,
                     float* img_out, float* mask_out, int B, int H, int W, pis_stream_t stream);
 
+/* The same batch, every entry resampled under its own affine map and tone curve (random rotation, scale,
+ * shift, flip, brightness: dataset.py:AffineAugment). Arguments as pis_cache_batch with sym replaced by
+ * params: B records of 32 bytes in device memory, 16-byte aligned, required:
+ *   int32 a[6]; float gain; float bias;
+ * The geometry is 16.16 fixed point, so that a host restatement (dataset.py:PackedSamples.warp) agrees
+ * bit for bit. For output pixel (y, x), with 64-bit integer sums:
+ *   SX = a[0]*x + a[1]*y + a[2]      SY = a[3]*x + a[4]*y + a[5]          source coordinates
+ *   x0 = SX >> 16, y0 = SY >> 16 (floor)     fx = (SX >> 8) & 255, fy = (SY >> 8) & 255
+ *   reflect(i, n) = 0 if n == 1, else m = i mod (2n - 2) >= 0, m < n ? m : 2n - 2 - m   (no repeated edge)
+ * u8 image:  I = (256-fy)*((256-fx)*v00 + fx*v01) + fy*((256-fx)*v10 + fx*v11) over the uint8 pixels at the
+ *            reflected (y0 | y0+1, x0 | x0+1), an exact integer below 2^24; t = float(I) * 2^-16;
+ *            img = (t - lo) / den
+ * f32 image: w00 = (256-fy)*(256-fx), w01 = (256-fy)*fx, w10 = fy*(256-fx), w11 = fy*fx as floats;
+ *            img = ((w00*v00 + w01*v01) + (w10*v10 + w11*v11)) * 2^-16
+ * mask:      the value (bit or float) at reflect((SY + 32768) >> 16, H), reflect((SX + 32768) >> 16, W)
+ * tone:      img_out = gain * img + bias, no clamp
+ * every float operation correctly rounded on its own (no fused multiply-add). The record
+ * {65536, 0, 0, 0, 65536, 0}, 1.0f, 0.0f gives what pis_cache_batch gives with sym == NULL.
+ * An idx outside [0, N) fills that entry's two outputs with NaN and reads nothing of the cache.
+ * PIS_ERR_ARG as pis_cache_batch, and for params NULL or not 16-byte aligned, and for H or W above 4096:
+ * with |a[k]| < 2^31 that bound keeps SX >> 16 and SY >> 16 inside 32 bits, where the reflection is done. */
+int pis_cache_batch_affine(const void* img, int img_fmt, size_t img_stride, const void* mask, int mask_fmt,
+                           size_t mask_stride, const float* norm, const int64_t* idx, const void* params,
+                           int64_t N, float* img_out, float* mask_out, int B, int H, int W, pis_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """CLI of the reference (main.py:5-102): same flags and defaults, training on
 the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
---device-cache, --augment {flip,d4}."""
+--device-cache, --augment {flip,d4,affine}."""
 import argparse
 
 from physics_informed_image_segmentation_amd.train import train
@@ -28,9 +28,9 @@ def parse_args(argv=None):
     p.add_argument("--device-cache", action="store_true",
                    help="preprocess the datasets once and serve every batch from a device-resident cache "
                         "(with --synthetic: the host disc dataset, cached, instead of the on-GPU generator)")
-    p.add_argument("--augment", choices=["flip", "d4"], default=None,
-                   help="random flips / all 8 grid symmetries per sample and epoch on the training loader "
-                        "(needs --device-cache)")
+    p.add_argument("--augment", choices=["flip", "d4", "affine"], default=None,
+                   help="random flips / all 8 grid symmetries / a random rotation, scale, shift, flip and "
+                        "brightness per sample and epoch on the training loader (needs --device-cache)")
     a = p.parse_args(argv)
     if a.augment and not a.device_cache:
         p.error("--augment needs --device-cache")

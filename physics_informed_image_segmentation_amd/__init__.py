@@ -10,7 +10,8 @@ matplotlib plotting helpers of src/plot.py (out of scope).
 """
 __version__ = "0.2.0"
 
-from .dataset import CellSegmentationDataset, DeviceCachedLoader, SyntheticDiscDataset, pack_samples  # noqa: E402
+from .dataset import (AffineAugment, CellSegmentationDataset, DeviceCachedLoader, SyntheticDiscDataset,  # noqa: E402
+                      pack_samples)
 from .evaluate import (boundary_counts, compare_models_statistically, compute_boundary_f1,  # noqa: E402
                        compute_boundary_f1_batch, compute_hausdorff_distance, compute_hausdorff_distance_batch,
                        compute_iou, compute_iou_batch, compute_statistics, evaluate_model, evaluate_on_test_set,
@@ -32,4 +33,5 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "run_repeated_evaluations", "AblationConfig", "run_ablation_variant", "run_ablation_study",
            # build additions
            "SyntheticDiscDataset", "count_parameters", "train_epoch", "AdamW", "boundary_counts",
-           "extract_boundaries_device", "compute_hausdorff_distance_batch", "DeviceCachedLoader", "pack_samples"]
+           "extract_boundaries_device", "compute_hausdorff_distance_batch", "DeviceCachedLoader", "pack_samples",
+           "AffineAugment"]

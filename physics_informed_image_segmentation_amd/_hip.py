@@ -100,6 +100,7 @@ _SIGNATURES = {
     "pis_boundary_ws": ([I, I, I], c_size_t),
     "pis_boundary_metrics": ([P, P, I, I, I, c_float, I, P, P, P, P, Z, P], c_int),
     "pis_cache_batch": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
+    "pis_cache_batch_affine": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

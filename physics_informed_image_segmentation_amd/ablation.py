@@ -252,14 +252,14 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                          learning_rate: float = 1e-4, stage1_epochs: int = 50, stage2_epochs: int = 50,
                          early_stopping_patience: int = 10, output_dir: Optional[Path] = None,
                          ablation_folder: Optional[Path] = None, num_workers: int = 2, boundary_metrics: bool = True,
-                         verbose: bool = False, device_cache: bool = False, augment: Optional[str] = None) -> Dict:
+                         verbose: bool = False, device_cache: bool = False, augment=None) -> Dict:
     """Train one variant and evaluate it on both test sets (src/ablation.py:157-1237); same
     positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead).
     ``device_cache=True`` keeps the four datasets resident on the GPU and assembles the batches there
     (``dataset.DeviceCachedLoader``; ``augment`` on the training loader only); a set that does not fit
     keeps its ``DataLoader``."""
     if augment is not None and not device_cache:
-        raise ValueError("augment needs device_cache=True (the symmetries are applied by the cache kernel)")
+        raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     data = _data_spec(train_dir, (train_json, val_dir, val_json, in_dist_test_dir, in_dist_test_json,
                                   out_dist_test_dir, out_dist_test_json))
     if device is None:

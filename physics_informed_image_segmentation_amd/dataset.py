@@ -8,15 +8,17 @@ per-image min-max) — host-side, outside the kernel path.
 ``DeviceDiscLoader`` rasterises the same samples on the GPU (§8(f) row 1).
 ``DeviceCachedLoader`` keeps any dataset, preprocessed once on the host
 (``pack_samples``), resident on the GPU and assembles every batch there
-(``pis_cache_batch``, csrc/cache.hip).
+(``pis_cache_batch``, csrc/cache.hip), optionally under a random affine and intensity
+augmentation per sample and epoch (``AffineAugment``, ``pis_cache_batch_affine``).
 """
 from __future__ import annotations
 
 import json
 import os
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from pathlib import Path
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -283,6 +285,125 @@ class PackedSamples(NamedTuple):
             mask = self.mask[i, :4 * n].view(np.float32).copy()
         return torch.from_numpy(img.reshape(1, H, W)), torch.from_numpy(mask.reshape(1, H, W))
 
+    def warp(self, i: int, record) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Sample ``i`` under one affine record (``affine_record``: int32 ``a[6]``, float32 gain and
+        bias), as the (1, H, W) float32 pair ``pis_cache_batch_affine`` writes. This is the
+        DEFINITION of the augmentation (include/pis_capi.h restates it) and the kernel's oracle:
+        int64 coordinates in 16.16 fixed point, float32 operations in the stated order, each
+        rounded on its own, so the two agree bit for bit.
+
+        For output pixel (y, x): ``SX = a0 x + a1 y + a2``, ``SY = a3 x + a4 y + a5``;
+        ``x0 = SX >> 16``, ``fx = (SX >> 8) & 255`` (likewise y); the image is the bilinear mix of the
+        four pixels at the reflected ``(y0 | y0 + 1, x0 | x0 + 1)`` with the 8-bit weights — for u8 an
+        exact integer sum ``I < 2^24``, ``t = float(I) * 2^-16``, ``(t - lo) / den``; for f32
+        ``((w00 v00 + w01 v01) + (w10 v10 + w11 v11)) * 2^-16`` — then ``gain * img + bias`` without
+        a clamp; the mask is the nearest value, at ``reflect((S + 32768) >> 16)``."""
+        H, W = self.size
+        n = H * W
+        rec = np.ascontiguousarray(record).view(np.int32).reshape(8)
+        a = rec[:6].astype(np.int64)
+        gain, bias = rec[6:].view(np.float32)
+        y, x = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+        SX = a[0] * x + a[1] * y + a[2]
+        SY = a[3] * x + a[4] * y + a[5]
+        x0, y0 = SX >> 16, SY >> 16
+        fx, fy = (SX >> 8) & 255, (SY >> 8) & 255
+        c0, c1 = reflect_index(x0, W), reflect_index(x0 + 1, W)
+        r0, r1 = reflect_index(y0, H), reflect_index(y0 + 1, H)
+        if self.image_format == "u8":
+            v = self.image[i, :n].reshape(H, W).astype(np.int64)
+            I = (256 - fy) * ((256 - fx) * v[r0, c0] + fx * v[r0, c1]) + fy * ((256 - fx) * v[r1, c0] + fx * v[r1, c1])
+            lo, den = self.norm[i]
+            img = (I.astype(np.float32) * np.float32(2.0 ** -16) - lo) / den
+        else:
+            v = self.image[i, :4 * n].view(np.float32).reshape(H, W)
+            f32 = lambda w: w.astype(np.float32)
+            top = f32((256 - fy) * (256 - fx)) * v[r0, c0] + f32((256 - fy) * fx) * v[r0, c1]
+            bot = f32(fy * (256 - fx)) * v[r1, c0] + f32(fy * fx) * v[r1, c1]
+            img = (top + bot) * np.float32(2.0 ** -16)
+        img = gain * img + bias
+        q = reflect_index((SY + 32768) >> 16, H) * W + reflect_index((SX + 32768) >> 16, W)
+        if self.mask_format == "bits":
+            mask = np.unpackbits(self.mask[i], bitorder="little")[:n].astype(np.float32)[q]
+        else:
+            mask = self.mask[i, :4 * n].view(np.float32)[q]
+        assert img.dtype == np.float32 and mask.dtype == np.float32
+        return (torch.from_numpy(np.ascontiguousarray(img).reshape(1, H, W)),
+                torch.from_numpy(np.ascontiguousarray(mask).reshape(1, H, W)))
+
+
+def reflect_index(i, n: int):
+    """Index (array) ``i`` reflected into [0, n) about the edge pixels, which are not repeated (the
+    loss stencils' boundary rule, ``np.pad(mode="reflect")``), any number of periods outside."""
+    i = np.asarray(i, dtype=np.int64)
+    if n == 1:
+        return np.zeros_like(i)
+    m = np.mod(i, 2 * n - 2)
+    return np.where(m < n, m, 2 * n - 2 - m)
+
+
+# one record of pis_cache_batch_affine: int32 a[6], float gain, float bias
+AFFINE_RECORD = np.dtype([("a", np.int32, 6), ("gain", np.float32), ("bias", np.float32)])
+AFFINE_MAX_SIZE = 4096  # pis_cache_batch_affine: keeps the source coordinates' integer parts in 32 bits
+
+
+def affine_record(size, rotate=0.0, scale=1.0, shift=(0.0, 0.0), flip=False, gain=1.0, bias=0.0) -> np.ndarray:
+    """Records (``AFFINE_RECORD``) of the forward map ``p_out = c + s R(theta) F (p_in - c) + shift`` on
+    an (H, W) = ``size`` grid: ``c = ((W - 1) / 2, (H - 1) / 2)``, points are (x, y), ``R`` turns x
+    towards y by ``rotate`` degrees, ``F`` flips x when ``flip``, ``shift`` = (dx, dy) in pixels. Every
+    argument may be an array of N values (``shift``: (N, 2)). A record holds the INVERSE map — the
+    kernel goes from output pixels to source coordinates — computed in float64, times 65536,
+    rounded with ``np.rint``; a coefficient that does not fit int32 raises ``ValueError``."""
+    H, W = size
+    th = np.deg2rad(np.asarray(rotate, np.float64))
+    s = np.asarray(scale, np.float64)
+    sh = np.asarray(shift, np.float64)
+    f = np.where(np.asarray(flip, bool), -1.0, 1.0)
+    th, s, f, dx, dy, gain, bias = np.broadcast_arrays(th, s, f, sh[..., 0], sh[..., 1], np.asarray(gain, np.float64),
+                                                       np.asarray(bias, np.float64))
+    cos, sin = np.cos(th), np.sin(th)
+    # (s R F)^-1 = F R(-theta) / s
+    m = np.stack([f * cos / s, f * sin / s, -sin / s, cos / s], -1)
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    ox, oy = cx + dx, cy + dy  # where the centre lands
+    off = np.stack([cx - (m[..., 0] * ox + m[..., 1] * oy), cy - (m[..., 2] * ox + m[..., 3] * oy)], -1)
+    a = np.rint(np.stack([m[..., 0], m[..., 1], off[..., 0], m[..., 2], m[..., 3], off[..., 1]], -1) * 65536.0) + 0.0
+    if not np.all(np.abs(a) < 2.0 ** 31):
+        raise ValueError("affine_record: a coefficient does not fit the 16.16 int32 record "
+                         f"(largest magnitude {np.abs(a).max() / 65536.0:g} pixels)")
+    rec = np.zeros(a.shape[:-1], AFFINE_RECORD)
+    rec["a"] = a.astype(np.int32)
+    rec["gain"] = gain + 0.0  # + 0.0: no negative zero, the identity record has one bit pattern
+    rec["bias"] = bias + 0.0
+    return rec
+
+
+@dataclass(frozen=True)
+class AffineAugment:
+    """Ranges of ``DeviceCachedLoader(augment=...)``'s random affine and intensity augmentation; each
+    sample draws anew every epoch (``DeviceCachedLoader.affine_params``):
+
+    rotate     uniform in +-``rotate`` degrees about the image centre
+    scale      log-uniform in [1 / ``scale``, ``scale``]
+    translate  uniform in +-``translate`` x (W, H)
+    flip       a W flip with probability 1/2 (with the rotation: every reflection)
+    gain       image x (1 +- ``gain``)
+    bias       image + (+-``bias``), no clamp
+
+    What falls outside the sample is its reflection. The defaults are a choice, not a measurement:
+    the full circle because cells have no canonical orientation, the rest mild; no training run has
+    tuned them."""
+    rotate: float = 180.0
+    scale: float = 1.25
+    translate: float = 0.1
+    flip: bool = True
+    gain: float = 0.1
+    bias: float = 0.05
+
+    def __post_init__(self):
+        if not (self.scale > 0 and self.rotate >= 0 and self.translate >= 0 and self.gain >= 0 and self.bias >= 0):
+            raise ValueError(f"AffineAugment: scale must be positive and the other ranges non-negative, got {self}")
+
 
 def _rows(rows, row_bytes: int) -> np.ndarray:
     out = np.zeros((len(rows), _pad16(row_bytes)), np.uint8)
@@ -352,6 +473,17 @@ def pack_samples(dataset, indices=None, workers: Optional[int] = None) -> Packed
 _AUGMENT_CODES = {None: 1, "flip": 4, "d4": 8}
 
 
+def _resolve_augment(augment):
+    """None, "flip", "d4" as they are; "affine" -> ``AffineAugment()``; an ``AffineAugment`` as it is."""
+    if isinstance(augment, AffineAugment):
+        return augment
+    if isinstance(augment, str) and augment == "affine":
+        return AffineAugment()
+    if augment is None or (isinstance(augment, str) and augment in _AUGMENT_CODES):
+        return augment
+    raise ValueError(f"augment must be None, 'flip', 'd4', 'affine' or an AffineAugment, got {augment!r}")
+
+
 def apply_symmetry(t: torch.Tensor, s: int) -> torch.Tensor:
     """Symmetry code ``s`` of ``pis_cache_batch`` on the last two dimensions: bit 0 flips W, bit 1
     flips H, then bit 2 transposes."""
@@ -385,17 +517,20 @@ class DeviceCachedLoader:
     ``augment``: None (default), "flip" (codes 0-3: W and H flips) or "d4" (codes 0-7, adds the
     transpose; square sizes only). Sample ``i``'s code in an epoch is entry ``i`` of one
     ``torch.randint`` over the whole dataset from a generator seeded by (seed, epoch), so it does
-    not depend on ``world``, ``rank`` or ``batch_size`` (``symmetry_codes``). A dataset
-    ``transform`` is evaluated once, at cache time: it must be deterministic."""
+    not depend on ``world``, ``rank`` or ``batch_size`` (``symmetry_codes``). "affine" or an
+    ``AffineAugment``: a random rotation, scale, shift, flip, gain and bias per sample and epoch
+    (``affine_params``, drawn the same way), resampled by ``pis_cache_batch_affine`` — bilinear image,
+    nearest mask, reflected borders, in fixed point, so a batch equals ``PackedSamples.warp`` of its
+    records bit for bit; ``augment`` then holds the ``AffineAugment``. A dataset ``transform`` is
+    evaluated once, at cache time: it must be deterministic."""
 
     CHUNK_BYTES = 64 << 20
 
     def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 42, rank: int = 0, world: int = 1,
                  drop_last: bool = False, device=None, workers: Optional[int] = None, max_bytes: Optional[int] = None,
-                 augment: Optional[str] = None):
+                 augment: Union[None, str, AffineAugment] = None):
         from . import _hip  # noqa: F401  (fail early when the library is missing)
-        if augment not in _AUGMENT_CODES:
-            raise ValueError(f"augment must be None, 'flip' or 'd4', got {augment!r}")
+        augment = _resolve_augment(augment)
         self.dataset, self.batch_size, self.seed = dataset, batch_size, seed
         self.shuffle, self.rank, self.world, self.drop_last = shuffle, rank, world, drop_last
         self.device = torch.device(device) if device is not None else torch.device("cuda")
@@ -406,6 +541,9 @@ class DeviceCachedLoader:
         self.size, self.image_format, self.mask_format = packed.size, packed.image_format, packed.mask_format
         if augment == "d4" and self.size[0] != self.size[1]:
             raise ValueError(f"augment='d4' transposes: it needs square samples, got {self.size[0]} x {self.size[1]}")
+        if self.affine and max(self.size) > AFFINE_MAX_SIZE:
+            raise ValueError(f"augment='affine' takes samples up to {AFFINE_MAX_SIZE} pixels a side, got "
+                             f"{self.size[0]} x {self.size[1]}")
         self.nbytes = packed.nbytes
         limit = self.default_max_bytes(self.device) if max_bytes is None else int(max_bytes)
         self.check_fits(self.nbytes, limit)
@@ -444,6 +582,10 @@ class DeviceCachedLoader:
             torch.cuda.current_stream(self.device).synchronize()  # the staging buffer is reused
         return dst
 
+    @property
+    def affine(self) -> bool:
+        return isinstance(self.augment, AffineAugment)
+
     def set_epoch(self, epoch: int):
         self.epoch = epoch
 
@@ -453,11 +595,30 @@ class DeviceCachedLoader:
     def __len__(self):
         return _num_batches(len(self.indices()), self.batch_size, self.drop_last)
 
+    def affine_params(self, epoch: Optional[int] = None) -> np.ndarray:
+        """The ``AFFINE_RECORD`` of every dataset sample (dataset-index order) in ``epoch`` (default:
+        the current one); ``.view(np.int32).reshape(-1, 8)`` is the kernel's view. Sample ``i``'s
+        seven draws are row ``i`` of one ``torch.rand(N, 7, dtype=float64)`` from a generator seeded
+        by (seed, epoch), so they do not depend on ``world``, ``rank`` or ``batch_size``. Without an
+        affine ``augment``: identity records."""
+        n = len(self.ids)
+        if not self.affine:
+            return affine_record(self.size, rotate=np.zeros(n))
+        au = self.augment
+        e = self.epoch if epoch is None else epoch
+        g = torch.Generator().manual_seed(self.seed * 1_000_003 + e)
+        u = 2.0 * torch.rand(n, 7, generator=g, dtype=torch.float64).numpy() - 1.0  # uniform in [-1, 1)
+        H, W = self.size
+        return affine_record(self.size, rotate=u[:, 0] * au.rotate, scale=np.exp(u[:, 1] * np.log(au.scale)),
+                             shift=np.stack([u[:, 2] * au.translate * W, u[:, 3] * au.translate * H], 1),
+                             flip=(u[:, 4] < 0.0) & bool(au.flip), gain=1.0 + u[:, 5] * au.gain,
+                             bias=u[:, 6] * au.bias)
+
     def symmetry_codes(self, epoch: Optional[int] = None) -> torch.Tensor:
         """uint8 code of every dataset sample (dataset-index order) in ``epoch`` (default: the
-        current one); all zero without ``augment``."""
+        current one); all zero without ``augment`` and under the affine one."""
         n = len(self.ids)
-        k = _AUGMENT_CODES[self.augment]
+        k = 1 if self.affine else _AUGMENT_CODES[self.augment]
         if k == 1:
             return torch.zeros(n, dtype=torch.uint8)
         e = self.epoch if epoch is None else epoch
@@ -470,6 +631,15 @@ class DeviceCachedLoader:
         idx = self.indices()
         m = len(idx)
         stop = m - (m % self.batch_size if self.drop_last else 0)
+        if self.affine:
+            # one host-to-device copy per epoch: a 32-byte record per entry (first: 16-byte aligned
+            # at every batch), then the int64 index list
+            plan = torch.empty(40 * m, dtype=torch.uint8, pin_memory=True)
+            ids = torch.tensor(idx, dtype=torch.int64)
+            rec = np.ascontiguousarray(self.affine_params()[ids.numpy()])
+            plan[:32 * m].copy_(torch.from_numpy(rec.view(np.uint8).reshape(-1)))
+            plan[32 * m:].view(torch.int64).copy_(ids)
+            return self._batches(plan.to(self.device, non_blocking=True), m, stop)
         # one host-to-device copy per epoch: the int64 index list, then one symmetry byte per entry
         plan = torch.empty(8 * m + (m if self.augment else 0), dtype=torch.uint8, pin_memory=True)
         ids = torch.tensor(idx, dtype=torch.int64)
@@ -484,12 +654,22 @@ class DeviceCachedLoader:
         H, W = self.size
         img_fmt = _hip.PIS_CACHE_IMG_U8 if self.image_format == "u8" else _hip.PIS_CACHE_IMG_F32
         mask_fmt = _hip.PIS_CACHE_MASK_BITS if self.mask_format == "bits" else _hip.PIS_CACHE_MASK_F32
-        idx_p, sym_p = plan_d.data_ptr(), (plan_d.data_ptr() + 8 * m if self.augment else 0)
         n, bs = self.image.shape[0], self.batch_size
+        affine = self.affine
+        if affine:
+            rec_p, idx_p = plan_d.data_ptr(), plan_d.data_ptr() + 32 * m
+        else:
+            idx_p, sym_p = plan_d.data_ptr(), (plan_d.data_ptr() + 8 * m if self.augment else 0)
         for k in range(0, stop, bs):
             b = min(bs, m - k)
             img = torch.empty(b, 1, H, W, device=self.device)
             mask = torch.empty(b, 1, H, W, device=self.device)
+            if affine:
+                _hip.call("pis_cache_batch_affine", self.image.data_ptr(), img_fmt, self.image.stride(0),
+                          self.mask.data_ptr(), mask_fmt, self.mask.stride(0), _hip.ptr(self.norm), idx_p + 8 * k,
+                          rec_p + 32 * k, n, img.data_ptr(), mask.data_ptr(), b, H, W, _hip.stream_handle(self.device))
+                yield img, mask
+                continue
             _hip.call("pis_cache_batch", self.image.data_ptr(), img_fmt, self.image.stride(0), self.mask.data_ptr(),
                       mask_fmt, self.mask.stride(0), _hip.ptr(self.norm), idx_p + 8 * k, sym_p + k if sym_p else 0,
                       n, img.data_ptr(), mask.data_ptr(), b, H, W, _hip.stream_handle(self.device))

@@ -447,7 +447,7 @@ def _loaders(train_ds, val_ds, batch_size: int, world: int, rank: int, workers: 
 
 
 def _cached_loaders(train_ds, val_ds, batch_size: int, world: int, rank: int, device, seed: int,
-                    augment: Optional[str], say=print):
+                    augment, say=print):
     """``device_cache=True``: both sets resident on the GPU, batches assembled there
     (``DeviceCachedLoader``; ``augment`` on the training loader only). None when a set does not
     fit (said, and the caller falls back to the ``DataLoader`` path)."""
@@ -472,7 +472,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           early_stopping_patience: int = 10, train_fraction: Optional[float] = None, seed: int = 42,
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
           num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
-          augment: Optional[str] = None):
+          augment=None):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -488,10 +488,10 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     DistributedSampler) unless ``device_data=False``; ``device_cache=True`` to preprocess the
     datasets once on the host and serve every batch from a device-resident cache
     (``DeviceCachedLoader``: the cell dataset, a ``train_fraction`` subset, or the disc dataset with
-    ``device_data=False``), with ``augment`` ("flip" / "d4") on its training loader; a cache that
+    ``device_data=False``), with ``augment`` ("flip" / "d4" / "affine" or a ``dataset.AffineAugment``) on its training loader; a cache that
     does not fit falls back to the ``DataLoader`` path."""
     if augment is not None and not device_cache:
-        raise ValueError("augment needs device_cache=True (the symmetries are applied by the cache kernel)")
+        raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     rank, local_rank, world = init_from_env()
     if not torch.cuda.is_available():
         raise _hip.HipError("train(): the MI355X path needs a GPU (no CPU fallback in this build)")

@@ -40,8 +40,9 @@ def main(argv=None):
     ap.add_argument("--num-workers", type=int, default=2)
     ap.add_argument("--device-cache", action="store_true",
                     help="preprocess the datasets once and serve every batch from a device-resident cache")
-    ap.add_argument("--augment", choices=["flip", "d4"], default=None,
-                    help="random flips / all 8 grid symmetries on the training loader (needs --device-cache)")
+    ap.add_argument("--augment", choices=["flip", "d4", "affine"], default=None,
+                    help="random flips / all 8 grid symmetries / a random rotation, scale, shift, flip and brightness on "
+                         "the training loader (needs --device-cache)")
     args = ap.parse_args(argv)
     if args.augment and not args.device_cache:
         ap.error("--augment needs --device-cache")

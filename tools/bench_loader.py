@@ -2,6 +2,7 @@
 
     python tools/bench_loader.py                    # both parts, both sizes -> profiles/device_cache.txt
     python tools/bench_loader.py --part a --out -   # kernel only, to stdout
+    python tools/bench_loader.py --part affine      # the affine augmentation -> profiles/device_cache_affine.txt
 
 The dataset is a COCO-style folder the tool writes into a temporary directory (--images grey
 PNGs with a few polygon annotations each), read through the unchanged ``CellSegmentationDataset``.
@@ -19,6 +20,14 @@ batches already resident on the device, ``DataLoader`` with 2 and with 16 worker
 ``persistent_workers``, so their start-up is not in the timed epochs and they hold no GPU).
 ``train_epoch`` ends in its host synchronisation: a host clock around it is the epoch time. The
 bar: cached >= 0.97 x resident list. The DataLoader rows are for the record.
+
+(affine) ``pis_cache_batch_affine`` with records drawn from the default ranges, against
+``pis_cache_batch`` without a symmetry and under the transpose code (its per-pixel gather): the
+three launches interleaved repetition by repetition, protocol of (a), ratios reported. Then
+``train_epoch`` images/s over a cached loader with ``augment="affine"`` and one without, alternating
+in one process, median and minimum of --rounds (at least 5) timed epochs each; the margin a
+difference has to leave to count is the plain loader's own spread. No bar is set: the figures are
+the record.
 """
 import argparse
 import json
@@ -123,6 +132,98 @@ def part_a(ds_at, reps, say):
     return ok
 
 
+def events_ms(fns, reps, flush=None, sink=None):
+    """``event_ms`` for several launches interleaved repetition by repetition: name -> median ms."""
+    evs = {k: [] for k in fns}
+    for _ in range(reps + 3):
+        for k, fn in fns.items():
+            if flush is not None:
+                torch.sum(flush, dim=0, out=sink)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            evs[k].append((e0, e1))
+    torch.cuda.synchronize()
+    return {k: statistics.median(a.elapsed_time(b) for a, b in v[3:]) for k, v in evs.items()}
+
+
+def part_affine(ds_at, reps, rounds, say):
+    from physics_informed_image_segmentation_amd import AdamW, DiceBCEPDELoss, UNet, _hip
+    from physics_informed_image_segmentation_amd.dataset import DeviceCachedLoader
+    from physics_informed_image_segmentation_amd.train import train_epoch
+    lib = _hip.lib()
+    st = _hip.stream_handle()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    flush = torch.ones(256 << 20, device="cuda")  # 1 GiB
+    sink = torch.empty((), device="cuda")
+    rounds = max(rounds, 5)
+    say("(affine) pis_cache_batch_affine (default ranges) vs pis_cache_batch without a symmetry and under the "
+        f"transpose code; launches interleaved, HIP events, median of {reps}")
+    loaders = {}
+    for B, H, W in SIZES:
+        ds = ds_at(H, W)
+        ld = DeviceCachedLoader(ds, B, shuffle=True, seed=1, augment="affine")
+        plain = DeviceCachedLoader(ds, B, shuffle=True, seed=1)
+        loaders[(B, H, W)] = (ds, ld, plain)
+        assert (ld.image_format, ld.mask_format) == ("u8", "bits")
+        n = ld.image.shape[0]
+        ids = ld.indices()[:B]
+        idx = torch.tensor(ids, dtype=torch.int64).cuda()
+        rec = torch.from_numpy(np.ascontiguousarray(ld.affine_params()[ids]).view(np.uint8).reshape(B, 32)).cuda()
+        sym = torch.full((B,), 4, dtype=torch.uint8).cuda()
+        img = torch.empty(B, 1, H, W, device="cuda")
+        mask = torch.empty_like(img)
+        head = (ld.image.data_ptr(), _hip.PIS_CACHE_IMG_U8, ld.image.stride(0), ld.mask.data_ptr(),
+                _hip.PIS_CACHE_MASK_BITS, ld.mask.stride(0), ld.norm.data_ptr(), idx.data_ptr())
+        tail = (n, img.data_ptr(), mask.data_ptr(), B, H, W, st)
+
+        def launch(fn, par):
+            if fn(*head, par, *tail) != 0:
+                raise RuntimeError(lib.pis_last_error().decode())
+        fns = {"copy": lambda: launch(lib.pis_cache_batch, 0),
+               "transpose": lambda: launch(lib.pis_cache_batch, sym.data_ptr()),
+               "affine": lambda: launch(lib.pis_cache_batch_affine, rec.data_ptr())}
+        for state, fl in (("cold", flush), ("warm", None)):
+            ms = events_ms(fns, reps, fl, sink)
+            say(f"  {B:3d} x {H}^2  {state}:  copy {ms['copy'] * 1e3:7.2f} us   transpose {ms['transpose'] * 1e3:7.2f} us   "
+                f"affine {ms['affine'] * 1e3:7.2f} us   affine / copy {ms['affine'] / ms['copy']:.2f}   "
+                f"affine / transpose {ms['affine'] / ms['transpose']:.2f}")
+    del flush
+    say(f"(affine) train_epoch images/s, augment='affine' vs augment=None alternating in one process, "
+        f"1 warm-up + {rounds} timed epochs each")
+    for (B, H, W), (ds, ld, plain) in loaders.items():
+        torch.manual_seed(42)
+        net = UNet(1, 1, 64).to(dev)
+        crit = DiceBCEPDELoss(pde_weight=1e-4, phase_field_weight=1e-4, diffusion_coeff=5.0, reaction_threshold=0.5,
+                              epsilon=0.05).to(dev)
+        opt = AdamW(net.parameters(), lr=1e-5, weight_decay=1e-5)
+        pair = {"augment=None": plain, "augment='affine'": ld}
+        times = {k: [] for k in pair}
+        for r in range(rounds + 1):
+            for name, loader in pair.items():
+                loader.set_epoch(r)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                train_epoch(net, loader, crit, opt, dev, return_components=True)
+                torch.cuda.synchronize()
+                if r:
+                    times[name].append(time.perf_counter() - t0)
+        n = len(ds)
+        say(f"  {B:3d} x {H}^2, {n} images per epoch")
+        rate = {}
+        for name, ts in times.items():
+            rate[name] = (n / statistics.median(ts), n / max(ts))
+            say(f"    {name:18s} median {rate[name][0]:9.1f}   minimum {rate[name][1]:9.1f} images/s   (epochs: "
+                + ", ".join(f"{t:.3f}" for t in ts) + " s)")
+        ts = times["augment=None"]
+        spread = (max(ts) - min(ts)) / statistics.median(ts)
+        diff = rate["augment='affine'"][0] / rate["augment=None"][0] - 1.0
+        say(f"    affine / None = {1.0 + diff:.4f} (median rates); the None rounds' own spread (max - min) / median = "
+            f"{spread:.4f}: the difference is {'inside' if abs(diff) <= spread else 'OUTSIDE'} it")
+    return True
+
+
 def part_b(ds_at, rounds, say):
     from torch.utils.data import DataLoader
 
@@ -178,13 +279,17 @@ def part_b(ds_at, rounds, say):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--part", choices=["a", "b", "all"], default="all")
+    ap.add_argument("--part", choices=["a", "b", "all", "affine"], default="all",
+                    help="all: a and b; affine: the affine augmentation's report (a file of its own)")
     ap.add_argument("--images", type=int, default=256, help="images in the generated dataset")
     ap.add_argument("--reps", type=int, default=50, help="timed launches per kernel figure")
     ap.add_argument("--rounds", type=int, default=3, help="timed epochs per loader")
-    ap.add_argument("--out", default=str(Path(__file__).resolve().parent.parent / "profiles" / "device_cache.txt"),
-                    help="report file ('-': stdout only)")
+    ap.add_argument("--out", default=None, help="report file ('-': stdout only; default: profiles/device_cache.txt, "
+                                                "profiles/device_cache_affine.txt for --part affine)")
     args = ap.parse_args(argv)
+    if args.out is None:
+        name = "device_cache_affine.txt" if args.part == "affine" else "device_cache.txt"
+        args.out = str(Path(__file__).resolve().parent.parent / "profiles" / name)
     if not torch.cuda.is_available():
         raise SystemExit("bench_loader.py: needs the MI355X (no CPU fallback)")
     from physics_informed_image_segmentation_amd.dataset import CellSegmentationDataset
@@ -193,7 +298,7 @@ def main(argv=None):
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    say(f"tools/bench_loader.py --images {args.images} --reps {args.reps} --rounds {args.rounds}   "
+    say(f"tools/bench_loader.py --part {args.part} --images {args.images} --reps {args.reps} --rounds {args.rounds}   "
         f"[{torch.cuda.get_device_name(0)}, torch {torch.__version__}]")
     with tempfile.TemporaryDirectory() as tmp:
         img_dir, ann = write_dataset(Path(tmp), args.images)
@@ -203,6 +308,8 @@ def main(argv=None):
             ok &= part_a(ds_at, args.reps, say)
         if args.part in ("b", "all"):
             ok &= part_b(ds_at, args.rounds, say)
+        if args.part == "affine":
+            ok &= part_affine(ds_at, args.reps, args.rounds, say)
     if args.out != "-":
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text("\n".join(lines) + "\n")
