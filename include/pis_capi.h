@@ -213,7 +213,20 @@ int pis_version(void);
                                   kernels (a full memory wait per patch row, the interior read twice);
                                   2 / 4: the dz pass / the input transform alone (the per-part A/B,
                                   profiles/r7_ab_wino_xform.txt) */
-#define PIS_TUNE_NKEYS 51
+#define PIS_TUNE_WINO_DGRAD_T 51 /* F(4x4,3x3) input gradients on the batched GEMM (not the fused contraction, the
+                                   direct kernel or F(6x6)): 1 the adjoint of the forward algorithm — the
+                                   contraction reads the weight gradient's E = G4 dz G4^T (one dz transform for
+                                   both gradients; pis_conv3x3_bwd_prep writes no V(dz)) with the filter
+                                   U' = G' g G'^T of the unrotated weights, and the output transform
+                                   overlap-adds the 6 x 6 patches (csrc/winograd.hip wino4_output_t_kernel: 64
+                                   loads per tile instead of 36, blocks in XCD-major order so that a tile's
+                                   neighbours share its L2; 2: the same without that order, its A/B); 0 V(dz) =
+                                   BT patch BT^T with the rotated filter. Default 1: C2 step 21.77 -> 21.46 ms in
+                                   one process, below in every round (profiles/r8_dgrad_t_ab.txt). Not bitwise
+                                   equal to 0 (both about 1.1e-6 from float64). The key must not
+                                   change between a pis_conv3x3_filter(s) / pis_conv3x3_bwd_prep and the
+                                   pis_conv3x3_dgrad_ex that consumes it (the latter is checked) */
+#define PIS_TUNE_NKEYS 52
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -317,7 +330,13 @@ int pis_conv3x3_wgrad_keep(const float* x, int ldx, const float* dz, int ldz, fl
  * transform into ws_dgrad (for pis_conv3x3_dgrad_ex) and the F(3x3,4x4) dz transform + bias
  * partials into ws_wgrad (for pis_conv3x3_wgrad_keep); both calls then pass PIS_WINO_PREPARED.
  * Returns 1 when done, 0 when this layer / workspace does not take that path (call without the
- * flag), < 0 on error. ws_wgrad must stay untouched until its pis_conv3x3_wgrad_keep ran. */
+ * flag), < 0 on error. ws_wgrad must stay untouched until its pis_conv3x3_wgrad_keep ran.
+ * With pis_tune key 51 and an input gradient on the batched GEMM, only the F(3x3,4x4) transform E is
+ * written (into ws_wgrad) and the prepared pis_conv3x3_dgrad_ex reads that same E in place: the
+ * library remembers, per ws_dgrad pointer and shape, where the last pis_conv3x3_bwd_prep put it.
+ * pis_conv3x3_wgrad_keep with PIS_WINO_PREPARED never writes the E region of ws_wgrad (it writes
+ * the split-K slabs, the reduced planes and the bias partials, all behind E), so the two consumers
+ * may run in either order or concurrently; ws_wgrad must then stay untouched until BOTH ran. */
 /* The F(4x4,3x3) filter transform of a conv3x3 layer, ahead of its convolution call (so it can run
  * on another stream, off the critical path). dgrad = 0: for the forward, w = KRSC [Cout][9][Cin];
  * dgrad = 1: for the input gradient, w = the ORIGINAL KRSC weights (rotated in place, as

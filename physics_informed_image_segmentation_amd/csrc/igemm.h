@@ -59,8 +59,11 @@ int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float*
                     hipStream_t s, float* tmax = nullptr);
 float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N);
 bool wino_fused_h3_planned(int B, int H, int W, int C, int N);
-// pis_conv3x3_bwd_prep's record of the V it wrote into ws (checked by the prepared dgrad)
-void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax);
+// pis_conv3x3_bwd_prep's record of the V it wrote into ws (checked by the prepared dgrad); e != NULL:
+// the overlap-add form (pis_tune key 51) — no V, the input gradient contracts the weight
+// gradient's E at e (C = Cout contraction channels, N = Cin)
+void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax, const float* e = nullptr);
+bool wino_dgrad_t_planned(int B, int H, int W, int C, int N);
 // does pis_conv3x3_dgrad_ex take F(4x4,3x3) Winograd for this layer with this workspace?
 bool dgrad_wino4_planned(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes);
 // Winograd weight-gradient pieces for tile edge m (2: F(3x3,2x2), 4: F(3x3,4x4)), nxi = (m+2)^2:

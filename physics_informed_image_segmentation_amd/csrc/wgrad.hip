@@ -1662,6 +1662,14 @@ extern "C" int pis_conv3x3_bwd_prep(const float* dz, int ldz, int B, int H, int 
   float* V = wino_v_slot(ws_dgrad, Cout, Cin);
   char* base = (char*)ws_wgrad;
   float* E = (float*)(base + wp.off_E);
+  if (wino_dgrad_t_planned(B, H, W, Cout, Cin)) {
+    // the overlap-add input gradient (pis_tune key 51) contracts E too: one set of planes, written
+    // once, read by both calls in place. pis_conv3x3_wgrad_keep with PIS_WINO_PREPARED only reads
+    // [off_E, off_part) (it writes the split slabs, M and the bias partials behind it).
+    const int rc = launch_wino_dz(dz, ldz, B, H, W, Cout, E, (hipStream_t)stream, 4, nullptr);
+    if (!rc) wino_prep_record(ws_dgrad, B, H, W, Cout, Cin, false, E);
+    return rc ? rc : 1;
+  }
   float* tmax = wino_fused_h3_planned(B, H, W, Cout, Cin) ? wino_tmax_slot(ws_dgrad, B, H, W, Cout, Cin) : nullptr;
   // (no bias partials: the weight gradient's GEMM sums them from E, wino_wgrad_plan gemm_bias)
   const int rc = launch_wino_dz2(dz, ldz, B, H, W, Cout, V, E, nullptr, (hipStream_t)stream, tmax);

@@ -294,6 +294,16 @@ __host__ __device__ constexpr float w4_at(int i, int k) {
                              {0.f, 1.f, -1.f, 0.125f, -8.f, 1.f}};
   return m[i][k];
 }
+// G' = D^-1 G with D = diag(1, 1/3, -1/3, -16/15, 1/15, 1), the row scales that make the weight
+// gradient's G4 = D AT^T (w4_g4 below, row by row). The overlap-add input gradient (pis_tune key
+// 51, wino4_output_t_kernel) contracts E = G4 e G4^T = (d_i d_j) (AT^T e AT)[i][j] instead of a
+// transform of its own, so its filter U' = G' g G'^T carries the inverse factor: U' (.) E = U (.)
+// (AT^T e AT) exactly (the factors are folded into the table, not multiplied at run time).
+__host__ __device__ constexpr float w4_gp(int i, int k) {
+  constexpr float m[6][3] = {{1.f, 0.f, 0.f},   {1.f, 1.f, 1.f},  {1.f, -1.f, 1.f},
+                             {1.f, 0.5f, 0.25f}, {1.f, -2.f, 4.f}, {0.f, 0.f, 1.f}};
+  return m[i][k];
+}
 // acc += c * v with the compile-time coefficient c folded (0: nothing, +-1: add/sub)
 template <typename T>
 __device__ __forceinline__ void axpy_c(T& acc, float c, const T& v) {
@@ -324,6 +334,9 @@ __device__ __forceinline__ void tile_decode(int64_t e, int c4n, int tpi, int64_t
 // U[xi][n][c] = (G g G^T)[xi], xi = 6 i + j, for the filter g of pair e = n C + c
 // With Up != NULL the transform is written as the bf16x6 hi/mid/lo planes Up[p][xi][n][c] instead
 // (the fused GEMM + output-transform kernel reads its B fragments straight from them).
+// GT: U' = G' g G'^T (w4_gp) of the ORIGINAL filter g, the overlap-add input gradient's operand
+// (fp32 planes only).
+template <bool GT = false>
 __device__ __forceinline__ void wino4_filter_item(const float (&g)[3][3], int64_t e, int n, int c, int N,
                                                   int64_t NC, float* __restrict__ U, int transposed,
                                                   __bf16* __restrict__ Up) {
@@ -334,7 +347,7 @@ __device__ __forceinline__ void wino4_filter_item(const float (&g)[3][3], int64_
     for (int s = 0; s < 3; ++s) {
       gg[i][s] = 0.f;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) axpy_c(gg[i][s], w4_g(i, k), g[k][s]);
+      for (int k = 0; k < 3; ++k) axpy_c(gg[i][s], GT ? w4_gp(i, k) : w4_g(i, k), g[k][s]);
     }
 #pragma unroll
   for (int i = 0; i < 6; ++i)
@@ -342,8 +355,8 @@ __device__ __forceinline__ void wino4_filter_item(const float (&g)[3][3], int64_
     for (int j = 0; j < 6; ++j) {
       float u = 0.f;
 #pragma unroll
-      for (int s = 0; s < 3; ++s) axpy_c(u, w4_g(j, s), gg[i][s]);
-      if (Up) {
+      for (int s = 0; s < 3; ++s) axpy_c(u, GT ? w4_gp(j, s) : w4_g(j, s), gg[i][s]);
+      if (!GT && Up) {
         const __bf16 h = (__bf16)u;
         const float r = u - (float)h;
         const __bf16 m = (__bf16)r;
@@ -360,23 +373,26 @@ __device__ __forceinline__ void wino4_filter_item(const float (&g)[3][3], int64_
 
 // w: KRSC weights [N][9][C] (row pitch ldw), already in the operand's orientation (the forward's
 // own weights, or pis_conv3x3_flip's copy for an input gradient). Block `bid` of `nblk`.
+// gt (w = a flipped copy): U' of the original filter, whose tap t is the copy's tap 8 - t — the
+// values and sums of wino4_filter_rot_tile's gt form, so the two are bitwise equal.
 __device__ __forceinline__ void wino4_filter_range(const float* __restrict__ w, int ldw, int N, int C,
                                                    float* __restrict__ U, int transposed, __bf16* __restrict__ Up,
-                                                   int bid, int nblk) {
+                                                   int bid, int nblk, int gt = 0) {
   const int64_t NC = (int64_t)N * C;
   for (int64_t e = (int64_t)bid * blockDim.x + threadIdx.x; e < NC; e += (int64_t)nblk * blockDim.x) {
     const int n = (int)(e / C), c = (int)(e - (int64_t)n * C);
     float g[3][3];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = w[(size_t)n * ldw + t * C + c];
-    wino4_filter_item(g, e, n, c, N, NC, U, transposed, Up);
+    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = w[(size_t)n * ldw + (gt ? 8 - t : t) * C + c];
+    if (gt) wino4_filter_item<true>(g, e, n, c, N, NC, U, transposed, nullptr);
+    else wino4_filter_item(g, e, n, c, N, NC, U, transposed, Up);
   }
 }
 
 __global__ __launch_bounds__(256) void wino4_filter_kernel(const float* __restrict__ w, int ldw, int N, int C,
                                                            float* __restrict__ U, int transposed = 0,
-                                                           __bf16* __restrict__ Up = nullptr) {
-  wino4_filter_range(w, ldw, N, C, U, transposed, Up, blockIdx.x, gridDim.x);
+                                                           __bf16* __restrict__ Up = nullptr, int gt = 0) {
+  wino4_filter_range(w, ldw, N, C, U, transposed, Up, blockIdx.x, gridDim.x, gt);
 }
 
 // The input-gradient filter transform straight from the layer's ORIGINAL KRSC weights [C][9][N]
@@ -387,9 +403,11 @@ __global__ __launch_bounds__(256) void wino4_filter_kernel(const float* __restri
 // output planes are written in runs along c as by wino4_filter_kernel.
 // sg: the calling kernel's one tap tile (the batch kernel shares it between the tile families)
 using FilterTapTile = float[9][32][33];  // [tap][c][n], padded: the transform reads along c conflict-free
+// gt: the overlap-add input gradient's U' = G' g G'^T of the UNROTATED filter (tap t as stored)
 __device__ __forceinline__ void wino4_filter_rot_tile(const float* __restrict__ w, int N, int C,
                                                       float* __restrict__ U, int transposed,
-                                                      __bf16* __restrict__ Up, int tile, FilterTapTile& sg) {
+                                                      __bf16* __restrict__ Up, int tile, FilterTapTile& sg,
+                                                      int gt = 0) {
   const int nb = N / 32, n0 = 32 * (tile % nb), c0 = 32 * (tile / nb);
   const int tid = threadIdx.x, lx = tid & 31, ly = tid >> 5;
 #pragma unroll
@@ -406,16 +424,17 @@ __device__ __forceinline__ void wino4_filter_rot_tile(const float* __restrict__ 
     const int c = lx, nl = ly + 8 * i, n = n0 + nl;
     float g[3][3];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = sg[8 - t][c][nl];
-    wino4_filter_item(g, (int64_t)n * C + c0 + c, n, c0 + c, N, NC, U, transposed, Up);
+    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = sg[gt ? t : 8 - t][c][nl];
+    if (gt) wino4_filter_item<true>(g, (int64_t)n * C + c0 + c, n, c0 + c, N, NC, U, transposed, nullptr);
+    else wino4_filter_item(g, (int64_t)n * C + c0 + c, n, c0 + c, N, NC, U, transposed, Up);
   }
 }
 
 __global__ __launch_bounds__(256) void wino4_filter_rot_kernel(const float* __restrict__ w, int N, int C,
                                                                float* __restrict__ U, int transposed,
-                                                               __bf16* __restrict__ Up) {
+                                                               __bf16* __restrict__ Up, int gt = 0) {
   __shared__ FilterTapTile sg;
-  wino4_filter_rot_tile(w, N, C, U, transposed, Up, blockIdx.x, sg);
+  wino4_filter_rot_tile(w, N, C, U, transposed, Up, blockIdx.x, sg, gt);
 }
 
 // The fused kernel's fp16x3 filter planes (pis_tune key 22), C % 64 == 0: one wave per output
@@ -807,6 +826,7 @@ struct FilterJobDev {
   void* out;
   int N, C, dgrad, planes, blocks;
   int tile;  // 4, or 6: the F(6x6,3x3) transform U[64][N][C] (planes 0)
+  int gt;    // dgrad, fp32 planes: the overlap-add input gradient's U' (wino4_filter_rot_tile)
 };
 constexpr int FILTER_MAX_JOBS = 40;
 struct FilterBatch {
@@ -827,7 +847,7 @@ __global__ __launch_bounds__(256) void wino4_filter_batch_kernel(FilterBatch fb)
     if (jb.dgrad) wino6_filter_rot_tile(jb.w, jb.N, jb.C, U, lb, sg);
     else wino6_filter_range(jb.w, 9 * jb.C, jb.N, jb.C, U, lb, jb.blocks);
   } else if (jb.planes == 2) wino4_filter_h2_wave(jb.w, 9 * jb.C, jb.N, jb.C, jb.dgrad, Up, 4 * lb + (threadIdx.x >> 6));
-  else if (jb.dgrad) wino4_filter_rot_tile(jb.w, jb.N, jb.C, U, 0, Up, lb, sg);
+  else if (jb.dgrad) wino4_filter_rot_tile(jb.w, jb.N, jb.C, U, 0, Up, lb, sg, jb.gt);
   else wino4_filter_range(jb.w, 9 * jb.C, jb.N, jb.C, U, 0, Up, lb, jb.blocks);
 }
 
@@ -964,6 +984,106 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
               max4<VW>(o[2 * qi][2 * qj], o[2 * qi][2 * qj + 1], o[2 * qi + 1][2 * qj], o[2 * qi + 1][2 * qj + 1]);
         }
     }
+  }
+}
+
+// ---- overlap-add output transform: the input gradient as the ADJOINT of the F(4x4,3x3) forward
+// (pis_tune key 51) ----
+// dx = sum_tiles scatter(BT^T M BT), M = sum_n U'[n][c] (.) E[n] with E the weight gradient's dz
+// transform (w4_gp): the 6 x 6 patch BT^T M BT of tile (ty, tx) lands on image rows 4 ty - 1 ..
+// 4 ty + 4, so the patches of neighbouring tiles overlap by their border ring. Columns 0 and 5 of
+// BT are e_0 and e_5, so patch row 0 is M[0][.] BT and row 5 is M[5][.] BT (columns alike): an
+// output 4 x 4 tile needs its own 36 M values, row 5 of the upper neighbour, row 0 of the lower,
+// column 5 of the left, column 0 of the right (6 each) and one corner value of each diagonal
+// neighbour — 64 values gathered into the 8 x 8 array z (index 0 / 7: the neighbours before
+// / after, 1..6: the own rows / columns), and y = OV^T z OV with
+//   OV[a][r] = BT[a - 1][r + 1] (a = 1..6),  OV[0][r] = [r == 0],  OV[7][r] = [r == 3].
+// Neighbours outside the image contribute nothing (tx == 0 has no left neighbour: t - 1 would be
+// the previous tile row's or image's last tile); their loads are redirected to the own tile and
+// zeroed by a select, so all 64 loads are issued branch-free before the first wait.
+__host__ __device__ constexpr float w4_ov(int a, int r) {
+  return a == 0 ? (r == 0 ? 1.f : 0.f) : a == 7 ? (r == 3 ? 1.f : 0.f) : w4_bt(a - 1, r + 1);
+}
+
+// xcd: blocks are dealt round-robin to the 8 XCDs (one L2 each), and a block holds one or two tiles
+// at 512 / 256 channels, so the lines of t +- 1 would be fetched by another XCD's L2 too; the block
+// order is made XCD-major (block b works as block (b % 8) (grid / 8) + b / 8), which keeps a tile's
+// neighbours on its own XCD except at the eight seams.
+template <int VW, bool MPF = false>
+__global__ __launch_bounds__(256) void wino4_output_t_kernel(const float* __restrict__ Mt, IGemmArgs g, int B,
+                                                             int xcd) {
+  const int N = g.N, n4n = N / VW, TW = g.W / 4, TH = g.H / 4;
+  const int64_t T = (int64_t)B * TH * TW, TN = T * N;
+  int bid = blockIdx.x;
+  if (xcd && gridDim.x % 8 == 0) bid = (bid & 7) * (int)(gridDim.x >> 3) + (bid >> 3);
+  for (int64_t e = (int64_t)bid * blockDim.x + threadIdx.x; e < T * n4n; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t t;
+    int n, b, rem;
+    tile_decode<VW>(e, n4n, TH * TW, t, n, b, rem);
+    const int ty = rem / TW, tx = rem - ty * TW;
+    fvec<VW> mk[4][4];
+    if constexpr (MPF) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const size_t pix = ((size_t)b * g.H + 4 * ty + i) * g.W + 4 * tx + j;
+          mk[i][j] = *reinterpret_cast<const fvec<VW>*>(g.mask + pix * g.ldm + n);
+        }
+    }
+    const bool in[8] = {ty > 0, true, true, true, true, true, true, ty + 1 < TH};  // rows of z
+    const bool jn[8] = {tx > 0, true, true, true, true, true, true, tx + 1 < TW};  // columns
+    const int64_t ro[3] = {in[0] ? -(int64_t)TW * N : 0, 0, in[7] ? (int64_t)TW * N : 0};
+    const int64_t co[3] = {jn[0] ? -(int64_t)N : 0, 0, jn[7] ? (int64_t)N : 0};
+    const float* p = Mt + t * N + n;
+    fvec<VW> z[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        // the neighbour this entry comes from (0 before, 1 own, 2 after) and its plane there
+        const int na = a == 0 ? 0 : a == 7 ? 2 : 1, nc = c == 0 ? 0 : c == 7 ? 2 : 1;
+        const int i = a == 0 ? 5 : a == 7 ? 0 : a - 1, j = c == 0 ? 5 : c == 7 ? 0 : c - 1;
+        z[a][c] = *reinterpret_cast<const fvec<VW>*>(p + (ro[na] + co[nc] + (int64_t)(6 * i + j) * TN));
+      }
+    __builtin_amdgcn_sched_barrier(0);  // all 64 loads issued before the first wait for one of them
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (a != 0 && a != 7 && c != 0 && c != 7) continue;
+        z[a][c] = (in[a] && jn[c]) ? z[a][c] : (fvec<VW>)0.f;
+      }
+    fvec<VW> y[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[i][j] = (fvec<VW>)0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {  // column c of z: its row transform, then its share of every y column
+      fvec<VW> r[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        r[i] = (fvec<VW>)0.f;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) axpy_c(r[i], w4_ov(a, i), z[a][c]);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) axpy_c(y[i][j], w4_ov(c, j), r[i]);
+    }
+    fvec<VW> bias4 = (fvec<VW>)0.f, sc4 = (fvec<VW>)1.f;
+    if (g.bias) bias4 = *reinterpret_cast<const fvec<VW>*>(g.bias + n);
+    if (g.flags & PIS_SCALE) sc4 = *reinterpret_cast<const fvec<VW>*>(g.scale + (size_t)b * N + n);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const size_t pix = ((size_t)b * g.H + 4 * ty + i) * g.W + 4 * tx + j;
+        if constexpr (MPF) conv_epilogue_vm<VW>(g, pix, n, y[i][j] + bias4, sc4, mk[i][j]);
+        else conv_epilogue4<VW>(g, pix, n, y[i][j] + bias4, sc4);
+      }
   }
 }
 
@@ -1215,6 +1335,32 @@ __global__ __launch_bounds__(256) void wino4_dz2_cols_kernel(const float* __rest
     wino4_dz_cols<VW>(d, E + t * N + n, TN, bsum);
     const float m = wino4_input_cols<VW, TM>(d, V + t * N + n, TN);
     if constexpr (TM) tile_max_store<VW>(m, N, n, t, tmax);
+  }
+  if (bpart) wino4_bias_partials<VW>(bsum, N, bpart);
+}
+
+// wino4_dz_kernel, single load phase: E alone (the overlap-add input gradient needs no V): the
+// 4 x 4 dz tile in one load phase, E by wino4_dz_cols — bitwise the E of every other dz pass
+template <int VW = 4>
+__global__ __launch_bounds__(256) void wino4_dz_cols_kernel(const float* __restrict__ dz, int ldz, int B, int H,
+                                                            int W, int N, float* __restrict__ E,
+                                                            float* __restrict__ bpart) {
+  const int nvn = N / VW, TW = W / 4, TH = H / 4;
+  const int64_t T = (int64_t)B * TH * TW, TN = T * N;
+  fvec<VW> bsum = (fvec<VW>)0.f;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < T * nvn; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t t;
+    int n, b, rem;
+    tile_decode<VW>(e, nvn, TH * TW, t, n, b, rem);
+    const int ty = rem / TW, tx = rem - ty * TW;
+    fvec<VW> d[6][6];  // only the interior [1..4][1..4] is loaded and read
+    const float* p = dz + (((size_t)b * H + 4 * ty) * W + 4 * tx) * ldz + n;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int l = 0; l < 4; ++l) d[k + 1][l + 1] = *reinterpret_cast<const fvec<VW>*>(p + ((size_t)k * W + l) * ldz);
+    __builtin_amdgcn_sched_barrier(0);
+    wino4_dz_cols<VW>(d, E + t * N + n, TN, bsum);
   }
   if (bpart) wino4_bias_partials<VW>(bsum, N, bpart);
 }
@@ -2350,6 +2496,19 @@ static void launch_wino4_output(const float* Mt, const IGemmArgs& a, int B, int6
     hipLaunchKernelGGL(wino4_output_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B);
 }
 
+// the overlap-add output transform of an input gradient whose contraction ran on E (pis_tune key 51)
+// (key 51 = 2: without the XCD-major block order, its A/B)
+static void launch_wino4_output_t(const float* Mt, const IGemmArgs& a, int B, int64_t T, int N, hipStream_t s) {
+  const int xcd = tune_get(PIS_TUNE_WINO_DGRAD_T) != 2;
+  if (tune_get(PIS_TUNE_WINO_VW) != 4)
+    if ((a.flags & PIS_MASK) && a.mask && tune_get(PIS_TUNE_WINO_OUT_MPF) != 0)
+      hipLaunchKernelGGL((wino4_output_t_kernel<2, true>), dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B, xcd);
+    else
+      hipLaunchKernelGGL(wino4_output_t_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B, xcd);
+  else
+    hipLaunchKernelGGL(wino4_output_t_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B, xcd);
+}
+
 // which of the F(4x4) input-side transforms take their single-load-phase form (pis_tune key 50):
 // 1 (default) both, 0 neither; 2 / 4 the merged dz pass / the input transform alone
 enum { XF_DZ2 = 2, XF_INPUT = 4 };
@@ -2379,17 +2538,19 @@ static void launch_wino4_input(int64_t T, int C, hipStream_t s, const float* x, 
 
 // the F(4x4,3x3) filter transform of a's weights (the tiled kernel for unflipped 32-aligned shapes)
 // (Up: the fused kernel's planes, bf16x6 or, with h2, fp16x3 + scales — C % 32 == 0)
+// gt (fp32 planes): the overlap-add input gradient's U' (a.wt: the original weights with
+// a.w_unflipped, else the flipped copy)
 static void launch_wino4_filter(const IGemmArgs& a, int N, int C, float* U, int transposed, __bf16* Up,
-                                hipStream_t s, bool h2 = false) {
+                                hipStream_t s, bool h2 = false, int gt = 0) {
   if (h2)  // C % 64 == 0, N % 4 == 0 (the fused kernel's shapes)
     hipLaunchKernelGGL(wino4_filter_h2_kernel, dim3(N / 4), dim3(256), 0, s, a.wt, a.ldw, N, C, a.w_unflipped ? 1 : 0,
                        Up);
   else if (a.w_unflipped)  // N, C % 32 == 0 checked by launch_wino3x3
     hipLaunchKernelGGL(wino4_filter_rot_kernel, dim3((N / 32) * (C / 32)), dim3(256), 0, s, a.wt, N, C, U,
-                       transposed, Up);
+                       transposed, Up, gt);
   else
     hipLaunchKernelGGL(wino4_filter_kernel, dim3(grid_of((int64_t)N * C)), dim3(256), 0, s, a.wt, a.ldw, N, C, U,
-                       transposed, Up);
+                       transposed, Up, gt);
 }
 
 // the fused 64 -> 64 kernel's arithmetic (pis_tune key 22): fp16x3 planes instead of bf16x6
@@ -2565,7 +2726,15 @@ size_t wino_ws_bytes(int B, int H, int W, int C, int N) {
   return wino6_layer(B, H, W, C, N) ? std::max(f4, wino6_ws_bytes(B, H, W, C, N)) : f4;
 }
 
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N);
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, const float** e);
+
+// pis_tune key 51: an F(4x4,3x3) input gradient on the batched GEMM (C = Cout contraction channels,
+// N = Cin; not the fused contraction, and the callers exclude the direct and F(6x6) layers) contracts
+// the weight gradient's E with U' and ends in the overlap-add transform (wino4_output_t_kernel)
+bool wino_dgrad_t_planned(int B, int H, int W, int C, int N) {
+  if (tune_get(PIS_TUNE_WINO_DGRAD_T) == 0 || wino_tile(H, W) != 4) return false;
+  return !wino_gemm_out_wanted(4, (int64_t)B * (H / 4) * (W / 4), C, N);
+}
 
 // a describes the direct conv (src/lds = input, wt/ldw = KRSC weights, N outputs, epilogue)
 int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v, bool v_ready) {
@@ -2576,8 +2745,9 @@ int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* ke
   float* V = U + (size_t)nxi * N * C;
   float* Mt = V + (size_t)nxi * T * C;
   if (keep_v && m == 4) V = keep_v;
+  const float* e_prep = nullptr;  // a prepared overlap-add input gradient's E (in the weight gradient's workspace)
   if (v_ready && m == 4) {
-    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N);
+    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N, &e_prep);
     if (rc) return rc;
   }
   // F(6x6,3x3): the deep layers' forward and input gradient (no kept or prepared F(4x4) transforms)
@@ -2606,7 +2776,15 @@ int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* ke
   if (v_ready && m != 4) return set_error("launch_wino3x3: prepared transforms need F(4x4,3x3)"), PIS_ERR_ARG;
   if (a.w_unflipped && (m != 4 || N % 32 || C % 32))
     return set_error("launch_wino3x3: unflipped weights need F(4x4,3x3) and 32-aligned channels"), PIS_ERR_ARG;
-  if (m == 4) {
+  // the overlap-add input gradient: the GEMM's A operand is E (the call's own, in V's place, or
+  // the one pis_conv3x3_bwd_prep left for the weight gradient too), its filter U'
+  const bool dgrad_t = m == 4 && a.is_dgrad && wino_dgrad_t_planned(B, a.H, a.W, C, N);
+  if (dgrad_t) {
+    if (a.filter_ready) U = const_cast<float*>(a.wt);
+    else launch_wino4_filter(a, N, C, U, 0, nullptr, s, false, 1);
+    if (v_ready) V = const_cast<float*>(e_prep);
+    else if (const int rc = launch_wino_dz(a.src, a.lds, B, a.H, a.W, C, V, s, 4, nullptr)) return rc;
+  } else if (m == 4) {
     if (a.filter_ready) U = const_cast<float*>(a.wt);
     else launch_wino4_filter(a, N, C, U, 0, nullptr, s);
     if (!v_ready) launch_wino4_input(T, C, s, a.src, a.lds, B, a.H, a.W, C, V, nullptr);
@@ -2676,7 +2854,9 @@ int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* ke
   launch_hook("wino_gemm", 1, s, flop);
   if (rc) return rc;
   gemm_done(s);
-  if (m == 4)
+  if (dgrad_t)
+    launch_wino4_output_t(Mt, a, B, T, N, s);
+  else if (m == 4)
     launch_wino4_output(Mt, a, B, T, N, s);
   else
     hipLaunchKernelGGL(wino_output_kernel, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B);
@@ -2701,7 +2881,9 @@ int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format
   if (format == 2 && wino_gemm_out_h3() && (C % 64 || N % 4))
     return set_error("pis_conv3x3_filter: fp16x3 planes need 64 x k contraction channels"), PIS_ERR_ARG;
   if (format == 2) launch_wino4_filter(a, N, C, nullptr, 0, reinterpret_cast<__bf16*>(out), s, wino_gemm_out_h3());
-  else launch_wino4_filter(a, N, C, reinterpret_cast<float*>(out), 0, nullptr, s);
+  else  // format 1 of an input gradient: the batched GEMM, so U' with key 51 (wino_dgrad_t_planned)
+    launch_wino4_filter(a, N, C, reinterpret_cast<float*>(out), 0, nullptr, s, false,
+                        dgrad && tune_get(PIS_TUNE_WINO_DGRAD_T) != 0);
   return launch_status("wino_filter");
 }
 
@@ -2720,7 +2902,8 @@ int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, co
     if (planes == 2 && (C[k] % 64 || N[k] % 4))
       return set_error("pis_conv3x3_filters: fp16x3 planes need 64 x k contraction channels"), PIS_ERR_ARG;
     const int blocks = planes == 2 ? N[k] / 4 : dgrad[k] ? (N[k] / 32) * (C[k] / 32) : grid_of((int64_t)N[k] * C[k]);
-    fb.j[k] = FilterJobDev{w[k], out[k], N[k], C[k], dgrad[k], planes, blocks, format[k] == 4 ? 6 : 4};
+    const int gt = dgrad[k] && format[k] == 1 && tune_get(PIS_TUNE_WINO_DGRAD_T) != 0;
+    fb.j[k] = FilterJobDev{w[k], out[k], N[k], C[k], dgrad[k], planes, blocks, format[k] == 4 ? 6 : 4, gt};
     fb.start[k] = total;
     total += blocks;
   }
@@ -2756,7 +2939,13 @@ int wino_dz_blocks_max(int B, int H, int W, int N, int m) {
 int launch_wino_dz(const float* dz, int ldz, int B, int H, int W, int N, float* E, hipStream_t s, int m,
                    float* bpart) {
   const int64_t T = (int64_t)B * (H / m) * (W / m);
-  if (m == 4 && dz_vw(N) == 2)
+  if (m == 4 && wino_xform(XF_DZ2) && dz_vw(N) == 2)
+    hipLaunchKernelGGL(wino4_dz_cols_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, dz, ldz, B, H, W, N, E,
+                       bpart);
+  else if (m == 4 && wino_xform(XF_DZ2))
+    hipLaunchKernelGGL(wino4_dz_cols_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, dz, ldz, B, H, W, N, E,
+                       bpart);
+  else if (m == 4 && dz_vw(N) == 2)
     hipLaunchKernelGGL(wino4_dz_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, dz, ldz, B, H, W, N, E, bpart);
   else if (m == 4)
     hipLaunchKernelGGL(wino4_dz_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, dz, ldz, B, H, W, N, E, bpart);
@@ -2795,21 +2984,28 @@ struct PrepRecord {
   const void* ws;
   int B, H, W, C, N;
   bool tmax;
+  const float* e;  // overlap-add form (key 51): no V in ws; the input gradient contracts this E
 };
 thread_local PrepRecord g_prep[16];
 thread_local int g_prep_next = 0;
 }  // namespace
 
-void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax) {
+void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax, const float* e) {
   for (auto& r : g_prep)
     if (r.ws == ws) r.ws = nullptr;  // the workspace's previous content is gone
-  g_prep[g_prep_next] = PrepRecord{ws, B, H, W, C, N, tmax};
+  g_prep[g_prep_next] = PrepRecord{ws, B, H, W, C, N, tmax, e};
   g_prep_next = (g_prep_next + 1) % 16;
 }
 
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N) {
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, const float** e) {
   for (const auto& r : g_prep)
     if (r.ws == ws && r.B == B && r.H == H && r.W == W && r.C == C && r.N == N) {
+      if ((r.e != nullptr) != wino_dgrad_t_planned(B, H, W, C, N))
+        return set_error("PIS_WINO_PREPARED: pis_conv3x3_bwd_prep wrote %s but this call's kernel choice reads %s "
+                         "(a pis_tune knob changed in between)",
+                         r.e ? "E alone" : "V(dz)", r.e ? "V(dz)" : "E"),
+               PIS_ERR_ARG;
+      *e = r.e;
       if (r.tmax != wino_fused_h3_planned(B, H, W, C, N))
         return set_error("PIS_WINO_PREPARED: pis_conv3x3_bwd_prep wrote %s tile maxima but this call's kernel "
                          "choice needs %s (a pis_tune knob changed in between)",

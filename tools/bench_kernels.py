@@ -5,6 +5,11 @@ value of one tuning knob (pis_tune key), in interleaved rounds inside one
 process (cdna_hip_programming.md §5.4 rule 24). Prints TFLOP/s per layer.
 
     python tools/bench_kernels.py [--key 4] [--variants 0,1,2] [--rounds 3] [--noload]
+
+--ops pdgrad: the engine's prepared input gradient (pis_conv3x3_bwd_prep + pis_conv3x3_dgrad_ex from
+the original weights), e.g. --key 51 --variants 0,1 --ops dgrad,pdgrad for the overlap-add input
+gradient against the V(dz) form: under rocprofv3 --kernel-trace a layer's dz pass, GEMM and output
+transform per variant.
 """
 import argparse
 import os
@@ -102,6 +107,14 @@ def main():
             "wgrad": lambda: lib.pis_conv3x3_wgrad(x.data_ptr(), cin, dz.data_ptr(), cout, dw.data_ptr(),
                                                    db.data_ptr(), B, H, H, cin, cout, 0, ws.data_ptr(), nws, s),
         }
+
+        def pdgrad():  # dz transform(s) into the two workspaces, then the input gradient that reads them
+            if lib.pis_conv3x3_bwd_prep(dz.data_ptr(), cout, B, H, H, cin, cout, wsx.data_ptr(), nwx, ws.data_ptr(),
+                                        nws, s) != 1:
+                return ops["dgrad"]()
+            return lib.pis_conv3x3_dgrad_ex(dz.data_ptr(), cout, w.data_ptr(), x.data_ptr(), cin, 0, dx.data_ptr(), cin,
+                                            B, H, H, cin, cout, dflags | 16 | 32, wsx.data_ptr(), nwx, s)
+        ops["pdgrad"] = pdgrad
         dbg = [int(d) for d in args.dbg.split(",") if d] or ([1] if args.noload else [])
         vlist = [(v, 0) for v in variants] + [(v, d) for d in dbg for v in variants]
         results = {}
