@@ -496,6 +496,47 @@ int pis_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, doub
                    double beta2, double eps, double weight_decay, double step_size, double bc2_sqrt,
                    double grad_scale, pis_stream_t stream);
 
+/* ---- global-norm gradient clipping and the non-finite step guard ----
+ * pis_grad_sumsq reads the flat gradient g once and leaves, on the device, what
+ * torch.nn.utils.clip_grad_norm_ and an isfinite check would have computed on the host:
+ *   seg_sumsq[s] = sum_{i < seg_len[s]} (double)g[seg_off[s] + i]^2          (float64, exact squares)
+ *   total = sum_s seg_sumsq[s]                                               (float64, in segment order)
+ *   norm  = sqrt(total) * grad_scale          (the norm of the gradient AdamW applies, g' = g * grad_scale)
+ *   c     = max_norm / (norm + 1e-6);  coef = (float)(c > 1 ? 1 : c)         (max_norm <= 0: coef = 1)
+ *   apply = !(flags & PIS_GRADNORM_SKIP_NONFINITE) || isfinite(total)
+ * and pis_adamw_step_clipped is pis_adamw_step with g' = (g * grad_scale) * coef, returning without a
+ * write to p, m or v when apply == 0. g itself is never written. With coef == 1 the update is bitwise
+ * pis_adamw_step's. Without the guard a non-finite norm gives coef = 0 (Inf) or NaN (NaN) as torch's
+ * formula does, and the step proceeds (0 * Inf = NaN reaches p, as it would with torch).
+ *
+ * seg_off / seg_len are DEVICE tables of n_seg segments in floats: offsets >= 0 and multiples of 4,
+ * lengths >= 1; nothing outside the segments is read (the padding between them may hold anything).
+ * A segment with a bad offset or length counts as NaN (with the guard: the step is skipped).
+ * Deterministic: a segment is cut into slices of 8192 floats, one partial per slice summed in a
+ * fixed order by one block, partials and segments combined in a fixed order; no atomics; the result
+ * does not depend on the grid and is bitwise equal run to run.
+ *
+ * record: 16 bytes {float coef; int apply; double norm}, written every call.
+ * stats: PIS_GRADNORM_NSTATS doubles the caller zeroes once and may zero again between calls:
+ *   [0] steps seen  [1] steps clipped (applied with coef < 1)  [2] steps skipped  [3] steps with a
+ *   finite norm  [4] sum of the finite norms  [5] largest finite norm  [6] the last norm  [7] the last coef.
+ * ws: pis_grad_sumsq_ws(n_seg, n_total) bytes, n_total >= the sum of the lengths; 16-byte aligned.
+ * The lengths live on the device, so the host can only refuse a workspace below
+ * pis_grad_sumsq_ws(n_seg, n_seg); one that is too small for the table makes the call a skipped
+ * step with a NaN norm (apply = 0 whatever the flags) instead of a write past its end.
+ * pis_grad_sumsq_ws answers 0 (and names itself in pis_last_error()) for n_seg <= 0 or n_total < n_seg. */
+#define PIS_GRADNORM_SKIP_NONFINITE 1
+#define PIS_GRADNORM_NSTATS 8
+size_t pis_grad_sumsq_ws(int n_seg, int64_t n_total);
+int pis_grad_sumsq(const float* g, const int64_t* seg_off, const int64_t* seg_len, int n_seg,
+                   double grad_scale, double max_norm /* <= 0: no clipping */,
+                   int flags /* PIS_GRADNORM_SKIP_NONFINITE */, double* seg_sumsq, void* record,
+                   void* stats, void* ws, size_t ws_bytes, pis_stream_t stream);
+int pis_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t n, double lr,
+                           double beta1, double beta2, double eps, double weight_decay,
+                           double step_size, double bc2_sqrt, double grad_scale, const void* record,
+                           pis_stream_t stream);
+
 /* ---- channel sums (bias gradients): out[c] (+)= sum_p src[p*ld + c] ----
  * ld >= C; ws holds at least pis_colsum_ws(npix, C) bytes. When C % 4 == 0, ld % 4 == 0 and src
  * and ws are 16-byte aligned (float4 loads); any other C, and out always, needs no alignment.

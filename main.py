@@ -1,6 +1,7 @@
 """CLI of the reference (main.py:5-102): same flags and defaults, training on
 the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
---device-cache, --augment {flip,d4,affine}."""
+--device-cache, --augment {flip,d4,affine}, --clip-grad-norm FLOAT,
+--skip-nonfinite."""
 import argparse
 
 from physics_informed_image_segmentation_amd.train import train
@@ -31,7 +32,13 @@ def parse_args(argv=None):
     p.add_argument("--augment", choices=["flip", "d4", "affine"], default=None,
                    help="random flips / all 8 grid symmetries / a random rotation, scale, shift, flip and "
                         "brightness per sample and epoch on the training loader (needs --device-cache)")
+    p.add_argument("--clip-grad-norm", type=float, default=None, metavar="FLOAT",
+                   help="clip the global L2 norm of the gradients to FLOAT inside the fused AdamW step (default: off)")
+    p.add_argument("--skip-nonfinite", action="store_true",
+                   help="skip an optimizer step whose gradient norm is Inf or NaN (default: off)")
     a = p.parse_args(argv)
+    if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
+        p.error("--clip-grad-norm must be positive")
     if a.augment and not a.device_cache:
         p.error("--augment needs --device-cache")
     return a
@@ -46,7 +53,8 @@ def main(argv=None):
                  early_stopping_patience=a.early_stopping_patience, train_fraction=a.train_fraction,
                  seed=a.seed, base_dir=a.base_dir,
                  synthetic=tuple(a.synthetic) if a.synthetic else None,
-                 device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment)
+                 device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment,
+                 max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ PIS_FILTER_READY = 64
 PIS_LOSS_ALL_TERMS, PIS_LOSS_CHAIN_SIGMOID, PIS_LOSS_NO_REACTION = 1, 2, 4
 PIS_TUNE_LAST_WGRAD_MAIN = 42  # include/pis_capi.h: host schedule knob (unet.py)
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
+PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
 LOSS_NTERMS = 8
 TERM_TOTAL, TERM_DICE, TERM_BCE, TERM_RD, TERM_PF, TERM_I, TERM_P, TERM_T = range(8)
 
@@ -91,6 +92,9 @@ _SIGNATURES = {
     "pis_head_loss_bwd": ([P, I, P, P, P, P, I, I, I, I, ctypes.POINTER(LossParams), P, P, P, I, P, P, I, P, Z,
                            P], c_int),
     "pis_adamw_step": ([P, P, P, P, L, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, P], c_int),
+    "pis_grad_sumsq_ws": ([I, L], c_size_t),
+    "pis_grad_sumsq": ([P, P, P, I, Dbl, Dbl, I, P, P, P, P, Z, P], c_int),
+    "pis_adamw_step_clipped": ([P, P, P, P, L, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, P, P], c_int),
     "pis_colsum_ws": ([L, I], c_size_t),
     "pis_colsum": ([P, I, L, I, P, I, P, Z, P], c_int),
     "pis_pde_fields": ([P, I, I, I, c_float, c_float, P, P, P, P], c_int),

@@ -252,12 +252,13 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                          learning_rate: float = 1e-4, stage1_epochs: int = 50, stage2_epochs: int = 50,
                          early_stopping_patience: int = 10, output_dir: Optional[Path] = None,
                          ablation_folder: Optional[Path] = None, num_workers: int = 2, boundary_metrics: bool = True,
-                         verbose: bool = False, device_cache: bool = False, augment=None) -> Dict:
+                         verbose: bool = False, device_cache: bool = False, augment=None,
+                         max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False) -> Dict:
     """Train one variant and evaluate it on both test sets (src/ablation.py:157-1237); same
     positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead).
     ``device_cache=True`` keeps the four datasets resident on the GPU and assembles the batches there
     (``dataset.DeviceCachedLoader``; ``augment`` on the training loader only); a set that does not fit
-    keeps its ``DataLoader``."""
+    keeps its ``DataLoader``. ``max_grad_norm`` / ``skip_nonfinite`` go to every stage's ``AdamW``."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     data = _data_spec(train_dir, (train_json, val_dir, val_json, in_dist_test_dir, in_dist_test_json,
@@ -296,7 +297,8 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                 "out_dist": evaluate_model(model, out_loader, device, 0.5, boundary_metrics)}
 
     def stage(criterion, epochs, name, csv_name):
-        opt = AdamW(model.parameters(), lr=learning_rate, weight_decay=1e-5)
+        opt = AdamW(model.parameters(), lr=learning_rate, weight_decay=1e-5, max_grad_norm=max_grad_norm,
+                    skip_nonfinite=skip_nonfinite)
         stop = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
         return train_stage(model, train_loader, val_loader, criterion.to(device), opt, device, num_epochs=epochs,
                            stage_name=name, early_stopping=stop, verbose=verbose,

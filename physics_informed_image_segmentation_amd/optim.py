@@ -7,10 +7,24 @@ p *= 1 - lr*wd; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
 p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps), scalars rounded to fp32 as torch
 rounds its Python floats. ``grad_scale`` multiplies the gradient inside the
 kernel (data-parallel averaging without an extra pass).
+
+``max_grad_norm`` (global L2 clipping, the ``clip_grad_norm_`` formula) and
+``skip_nonfinite`` (skip the step when the gradient norm is Inf or NaN) turn on
+the norm path: one deterministic float64 sum of squares over the gradient arena
+(``pis_grad_sumsq``) leaves the clip coefficient and the skip decision on the
+device, and the AdamW launch (``pis_adamw_step_clipped``) reads them there. No
+host synchronisation, no second pass, and the gradient arena is not rescaled:
+``p.grad`` after ``step()`` still holds the unclipped gradients. The norm is
+that of ``grad_scale * g``, the gradient AdamW applies. With clipping on and
+the guard off a non-finite norm behaves as torch's formula does (coefficient 0
+for Inf, NaN for NaN; the NaN reaches the weights). A skipped step still
+advances the step counter and so the bias corrections: the kernel's scalars
+are rounded on the host exactly as torch rounds its Python floats, which a
+device-side count (a device ``pow``) could not promise bit for bit.
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
@@ -19,11 +33,16 @@ from . import _hip
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0):
+                 eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         if lr < 0 or eps < 0 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameter")
+        if max_grad_norm is not None and not max_grad_norm > 0:  # <= 0 and NaN
+            raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
         self._flat = {}  # group index -> (arena tensor, m, v, offsets) when every param views one arena
 
     # ---- arena discovery ------------------------------------------------------
@@ -93,6 +112,21 @@ class AdamW(torch.optim.Optimizer):
             arena, m, v, offs = st["arena"], st["m"], st["v"], st["offs"]
             g_flat = self._grad_arena(params, offs, arena)
             stream = _hip.stream_handle()
+            if self.norm_path:
+                if g_flat is None or not all(with_grad):
+                    raise NotImplementedError(
+                        "AdamW(max_grad_norm / skip_nonfinite) needs the flat path: every parameter with a "
+                        ".grad that views one gradient arena at its parameter's offset")
+                nb = self._norm_buffers(st, params)
+                _hip.call("pis_grad_sumsq", g_flat.data_ptr(), nb["off"].data_ptr(), nb["len"].data_ptr(),
+                          len(params), self.grad_scale, self.max_grad_norm or 0.0,
+                          _hip.PIS_GRADNORM_SKIP_NONFINITE if self.skip_nonfinite else 0,
+                          nb["sumsq"].data_ptr(), nb["record"].data_ptr(), nb["stats"].data_ptr(),
+                          nb["ws"].data_ptr(), nb["ws"].numel(), stream)
+                _hip.call("pis_adamw_step_clipped", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(),
+                          v.data_ptr(), arena.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt,
+                          self.grad_scale, nb["record"].data_ptr(), stream)
+                continue
             if g_flat is not None and all(with_grad):
                 _hip.call("pis_adamw_step", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(), v.data_ptr(),
                           arena.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale, stream)
@@ -106,6 +140,66 @@ class AdamW(torch.optim.Optimizer):
                 _hip.call("pis_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr() + 4 * o, v.data_ptr() + 4 * o,
                           p.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale, stream)
         return loss
+
+    # ---- gradient norm, clipping, step guard -----------------------------------
+    @property
+    def norm_path(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _norm_buffers(self, st, params):
+        """Segment table, record, statistics and workspace of one flat state, allocated once."""
+        nb = st.get("norm")
+        if nb is None:
+            dev = st["arena"].device
+            lens = [p.numel() for p in params]
+            ws_bytes = _hip.lib().pis_grad_sumsq_ws(len(params), sum(lens))
+            nb = {"off": torch.tensor(st["offs"], dtype=torch.int64, device=dev),
+                  "len": torch.tensor(lens, dtype=torch.int64, device=dev),
+                  "sumsq": torch.zeros(len(params), dtype=torch.float64, device=dev),
+                  "record": torch.zeros(2, dtype=torch.float64, device=dev),  # {float coef; int apply; double norm}
+                  "stats": torch.zeros(_hip.PIS_GRADNORM_NSTATS, dtype=torch.float64, device=dev),
+                  "ws": torch.empty((ws_bytes + 15) // 16 * 16, dtype=torch.uint8, device=dev)}
+            st["norm"] = nb
+        return nb
+
+    def _norm_state(self):
+        if not self.norm_path:
+            raise RuntimeError("grad_stats: the optimizer was built without max_grad_norm or skip_nonfinite")
+        sts = [st for st in self._flat.values() if "norm" in st]
+        if len(sts) != 1:
+            raise RuntimeError("grad_stats: one parameter group that has taken a step is needed" if not sts
+                               else "grad_stats: one parameter group expected")
+        return sts[0]["norm"]
+
+    def grad_stats(self) -> Dict[str, torch.Tensor]:
+        """Device tensors of the last step and the running counters; reading them is the caller's
+        synchronisation, producing them is none. ``total_norm`` (float64 scalar) and ``per_tensor_norm``
+        (float64 [n_params], in ``params`` order) are norms of ``grad_scale * g``; ``clip_coef`` is the
+        fp32 coefficient the update used; ``applied`` is 0 when the step was skipped. ``steps``,
+        ``clipped_steps``, ``skipped_steps``, ``finite_steps``, ``norm_sum`` and ``norm_max`` count
+        since the last ``pop_grad_stats()`` (sums and maximum over the steps with a finite norm)."""
+        nb = self._norm_state()
+        stats = nb["stats"]
+        return {"total_norm": nb["record"][1].clone(),
+                "clip_coef": nb["record"][:1].view(torch.float32)[0].clone(),
+                "applied": nb["record"][:1].view(torch.int32)[1].clone(),
+                "per_tensor_norm": nb["sumsq"].sqrt() * self.grad_scale,
+                "steps": stats[0].clone(), "clipped_steps": stats[1].clone(), "skipped_steps": stats[2].clone(),
+                "finite_steps": stats[3].clone(), "norm_sum": stats[4].clone(), "norm_max": stats[5].clone()}
+
+    def pop_grad_stats(self) -> Dict[str, float]:
+        """The counters and sums as Python numbers, zeroed afterwards: one host synchronisation, meant
+        for the end of an epoch. Before the first step everything is 0."""
+        if not any("norm" in st for st in self._flat.values()):
+            if not self.norm_path:
+                raise RuntimeError("pop_grad_stats: the optimizer was built without max_grad_norm or skip_nonfinite")
+            vals = [0.0] * _hip.PIS_GRADNORM_NSTATS
+        else:
+            stats = self._norm_state()["stats"]
+            vals = stats.tolist()
+            stats.zero_()
+        return {"steps": int(vals[0]), "clipped_steps": int(vals[1]), "skipped_steps": int(vals[2]),
+                "finite_steps": int(vals[3]), "norm_sum": vals[4], "norm_max": vals[5], "last_norm": vals[6]}
 
     @staticmethod
     def _grad_arena(params, offs, arena) -> Optional[torch.Tensor]:

@@ -283,7 +283,9 @@ def train_epoch(model, dataloader, criterion, optimizer, device, return_componen
     loss terms averaged over batches, Dice / IoU / boundary F1 over samples. Boundary F1
     (src/train.py:156) is scored on the GPU in the step's stream (``_BoundaryF1Device``) or, for
     host tensors and ``boundary_backend="host"``, on host threads beside the GPU
-    (``_BoundaryF1Async``); ``boundary_metrics=False`` reports 0.0 instead."""
+    (``_BoundaryF1Async``); ``boundary_metrics=False`` reports 0.0 instead. An
+    optimizer with ``max_grad_norm`` or ``skip_nonfinite`` set adds ``grad_norm`` (mean over the steps
+    with a finite norm), ``grad_norm_max``, ``clipped_steps`` and ``skipped_steps``."""
     model.train()
     meter = _Meter(device)
     bf1 = _boundary_scorer(device, boundary_backend) if compute_metrics and boundary_metrics else None
@@ -306,7 +308,14 @@ def train_epoch(model, dataloader, criterion, optimizer, device, return_componen
     finally:
         if bf1 is not None:
             bf1.close()
-    return _results(meter, criterion, return_components, compute_metrics, val=False)
+    out = _results(meter, criterion, return_components, compute_metrics, val=False)
+    if getattr(optimizer, "norm_path", False):  # read after the epoch's one synchronisation (_Meter.reduce)
+        gs = optimizer.pop_grad_stats()
+        out["grad_norm"] = gs["norm_sum"] / gs["finite_steps"] if gs["finite_steps"] else 0.0
+        out["grad_norm_max"] = gs["norm_max"]
+        out["clipped_steps"] = gs["clipped_steps"]
+        out["skipped_steps"] = gs["skipped_steps"]
+    return out
 
 
 @torch.no_grad()
@@ -375,6 +384,9 @@ def train_stage(model, train_loader, val_loader, criterion, optimizer, device, n
             for key, label in (("dice_loss", "Dice Loss"), ("bce_loss", "BCE Loss"), ("pde_loss", "PDE Loss")):
                 if key in tr:
                     print(f"    - {label}: {tr[key]:.6f}")
+            if "grad_norm" in tr:
+                print(f"  Grad norm: mean {tr['grad_norm']:.6f} max {tr['grad_norm_max']:.6f}"
+                      f"  clipped steps: {tr['clipped_steps']}  skipped steps: {tr['skipped_steps']}")
             print(f"  Val Loss: {va['loss']:.6f}")
             print(f"  Val Dice Score: {va['dice_score']:.6f}")
             for key, label in (("dice_loss", "Dice Loss"), ("bce_loss", "BCE Loss"), ("pde_loss", "PDE Loss")):
@@ -472,7 +484,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           early_stopping_patience: int = 10, train_fraction: Optional[float] = None, seed: int = 42,
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
           num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
-          augment=None):
+          augment=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -489,7 +501,9 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     datasets once on the host and serve every batch from a device-resident cache
     (``DeviceCachedLoader``: the cell dataset, a ``train_fraction`` subset, or the disc dataset with
     ``device_data=False``), with ``augment`` ("flip" / "d4" / "affine" or a ``dataset.AffineAugment``) on its training loader; a cache that
-    does not fit falls back to the ``DataLoader`` path."""
+    does not fit falls back to the ``DataLoader`` path. ``max_grad_norm`` (global L2 gradient clipping)
+    and ``skip_nonfinite`` (skip a step whose gradient norm is Inf or NaN) go to both stages'
+    ``AdamW``; off by default."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     rank, local_rank, world = init_from_env()
@@ -552,7 +566,8 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     grad_scale = 1.0 / world
 
     def run(criterion, lr, epochs, name, csv_path):
-        opt = AdamW(model.parameters(), lr=lr, weight_decay=1e-5, grad_scale=grad_scale)
+        opt = AdamW(model.parameters(), lr=lr, weight_decay=1e-5, grad_scale=grad_scale,
+                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         stopper = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
         return train_stage(model, train_loader, val_loader, criterion, opt, device, num_epochs=epochs,
                            stage_name=name, early_stopping=stopper, verbose=True, csv_path=csv_path)
