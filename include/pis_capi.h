@@ -537,6 +537,29 @@ int pis_adamw_step_clipped(float* p, const float* g, float* m, float* v, int64_t
                            double step_size, double bc2_sqrt, double grad_scale, const void* record,
                            pis_stream_t stream);
 
+/* ---- exponential moving average of the weights in the AdamW launch ----
+ * pis_adamw_step_ema updates p, m and v exactly as pis_adamw_step does (record == NULL) or as
+ * pis_adamw_step_clipped does (record: the 16 bytes pis_grad_sumsq left on the device), with the
+ * same host rounding of the scalars: the three arrays come out bitwise equal to those launches'.
+ * The thread that holds the new p then moves the average towards it, w = (float)ema_weight:
+ *   e = w < 0.5 ? e + w (p_new - e) : p_new - (p_new - e)(1 - w)            (torch.lerp's two forms)
+ * i.e. e + w (p_new - e) in exact arithmetic; w = 0 leaves e and w = 1 gives e = p_new, bit for bit.
+ * What is bitwise: p, m, v; e at w = 0 and w = 1. What is bounded: e otherwise, within the fp32
+ * rounding of one lerp per step (the compiler may contract it into an FMA, torch rounds twice).
+ * With a record whose apply == 0 the launch writes nothing: a skipped step does not move the average.
+ * ema_weight outside [0, 1] or NaN, a null pointer, n < 0, a buffer that is not 16-byte aligned and a
+ * record that is not 8-byte aligned are PIS_ERR_ARG; n == 0 is PIS_OK without a launch.
+ *
+ * pis_arena_exchange swaps the contents of a and b as raw 32-bit words (NaN payloads and -0.0
+ * survive). Equal or overlapping ranges, a buffer that is not 16-byte aligned and n < 0 are
+ * PIS_ERR_ARG; n == 0 is a no-op. Addresses do not change hands: views into either array, filter-job
+ * tables and captured graphs stay valid. */
+int pis_adamw_step_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, double step_size,
+                       double bc2_sqrt, double grad_scale, double ema_weight,
+                       const void* record /* NULL, or pis_grad_sumsq's record */, pis_stream_t stream);
+int pis_arena_exchange(float* a, float* b, int64_t n, pis_stream_t stream);
+
 /* ---- channel sums (bias gradients): out[c] (+)= sum_p src[p*ld + c] ----
  * ld >= C; ws holds at least pis_colsum_ws(npix, C) bytes. When C % 4 == 0, ld % 4 == 0 and src
  * and ws are 16-byte aligned (float4 loads); any other C, and out always, needs no alignment.

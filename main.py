@@ -1,7 +1,7 @@
 """CLI of the reference (main.py:5-102): same flags and defaults, training on
 the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
 --device-cache, --augment {flip,d4,affine}, --clip-grad-norm FLOAT,
---skip-nonfinite."""
+--skip-nonfinite, --ema-decay FLOAT, --no-ema-warmup."""
 import argparse
 
 from physics_informed_image_segmentation_amd.train import train
@@ -36,9 +36,16 @@ def parse_args(argv=None):
                    help="clip the global L2 norm of the gradients to FLOAT inside the fused AdamW step (default: off)")
     p.add_argument("--skip-nonfinite", action="store_true",
                    help="skip an optimizer step whose gradient norm is Inf or NaN (default: off)")
+    p.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                   help="keep an exponential moving average of the weights with decay FLOAT in (0, 1) inside the "
+                        "fused AdamW step; validation, early stopping and evaluation use it (default: off)")
+    p.add_argument("--no-ema-warmup", action="store_true",
+                   help="use --ema-decay from the first step instead of min(decay, (1 + k) / (10 + k))")
     a = p.parse_args(argv)
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
         p.error("--clip-grad-norm must be positive")
+    if a.ema_decay is not None and not 0.0 < a.ema_decay < 1.0:
+        p.error("--ema-decay must be in (0, 1)")
     if a.augment and not a.device_cache:
         p.error("--augment needs --device-cache")
     return a
@@ -54,7 +61,8 @@ def main(argv=None):
                  seed=a.seed, base_dir=a.base_dir,
                  synthetic=tuple(a.synthetic) if a.synthetic else None,
                  device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment,
-                 max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite)
+                 max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
+                 ema_decay=a.ema_decay, ema_warmup=not a.no_ema_warmup)
 
 
 if __name__ == "__main__":

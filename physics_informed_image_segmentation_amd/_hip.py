@@ -95,6 +95,8 @@ _SIGNATURES = {
     "pis_grad_sumsq_ws": ([I, L], c_size_t),
     "pis_grad_sumsq": ([P, P, P, I, Dbl, Dbl, I, P, P, P, P, Z, P], c_int),
     "pis_adamw_step_clipped": ([P, P, P, P, L, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, P, P], c_int),
+    "pis_adamw_step_ema": ([P, P, P, P, P, L, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, Dbl, P, P], c_int),
+    "pis_arena_exchange": ([P, P, L, P], c_int),
     "pis_colsum_ws": ([L, I], c_size_t),
     "pis_colsum": ([P, I, L, I, P, I, P, Z, P], c_int),
     "pis_pde_fields": ([P, I, I, I, c_float, c_float, P, P, P, P], c_int),

@@ -16,6 +16,7 @@ dataset is absent.
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import json
 from dataclasses import asdict, dataclass
@@ -253,12 +254,15 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                          early_stopping_patience: int = 10, output_dir: Optional[Path] = None,
                          ablation_folder: Optional[Path] = None, num_workers: int = 2, boundary_metrics: bool = True,
                          verbose: bool = False, device_cache: bool = False, augment=None,
-                         max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False) -> Dict:
+                         max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                         ema_decay: Optional[float] = None, ema_warmup: bool = True) -> Dict:
     """Train one variant and evaluate it on both test sets (src/ablation.py:157-1237); same
     positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead).
     ``device_cache=True`` keeps the four datasets resident on the GPU and assembles the batches there
     (``dataset.DeviceCachedLoader``; ``augment`` on the training loader only); a set that does not fit
-    keeps its ``DataLoader``. ``max_grad_norm`` / ``skip_nonfinite`` go to every stage's ``AdamW``."""
+    keeps its ``DataLoader``. ``max_grad_norm`` / ``skip_nonfinite`` go to every stage's ``AdamW``, and so do
+    ``ema_decay`` / ``ema_warmup``: each stage then validates on its exponential moving average of the
+    weights and the test-set evaluations that follow a stage run on that average (``optim.AdamW``)."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     data = _data_spec(train_dir, (train_json, val_dir, val_json, in_dist_test_dir, in_dist_test_json,
@@ -292,13 +296,17 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
     in_loader, out_loader = mk(in_ds, False), mk(out_ds, False)
     model = UNet(1, 1, 64).to(device)
 
+    opts = []  # the stages' optimizers: the last one holds the current average
+
     def evaluate():
-        return {"in_dist": evaluate_model(model, in_loader, device, 0.5, boundary_metrics),
-                "out_dist": evaluate_model(model, out_loader, device, 0.5, boundary_metrics)}
+        with opts[-1].averaged_weights() if ema_decay is not None and opts else contextlib.nullcontext():
+            return {"in_dist": evaluate_model(model, in_loader, device, 0.5, boundary_metrics),
+                    "out_dist": evaluate_model(model, out_loader, device, 0.5, boundary_metrics)}
 
     def stage(criterion, epochs, name, csv_name):
         opt = AdamW(model.parameters(), lr=learning_rate, weight_decay=1e-5, max_grad_norm=max_grad_norm,
-                    skip_nonfinite=skip_nonfinite)
+                    skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
+        opts.append(opt)
         stop = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
         return train_stage(model, train_loader, val_loader, criterion.to(device), opt, device, num_epochs=epochs,
                            stage_name=name, early_stopping=stop, verbose=verbose,

@@ -43,7 +43,12 @@ class StepGraph:
     (``_hip.OwnedStream``, recycled only into other owned streams, never destroyed) — and releases
     them in ``close()`` only after the device is idle: the graph, the loss and its autograd graph,
     the events, the engine, then the stream. ``close()`` also runs when the StepGraph is garbage
-    collected without it."""
+    collected without it.
+
+    AdamW runs eagerly after each replay, outside the graph, so an optimizer with ``ema_decay``
+    needs nothing here. ``optimizer.averaged_weights()`` exchanges the contents of the parameter
+    arena and the average, so the captured addresses stay valid and validation between two
+    ``step()`` calls is fine; the exchange must not be issued between a capture's begin and end."""
 
     def __init__(self, model: UNet, criterion, optimizer, x: torch.Tensor, target: torch.Tensor, warmup: int = 2,
                  fused_loss: bool = False, before_capture=None):

@@ -21,9 +21,22 @@ for Inf, NaN for NaN; the NaN reaches the weights). A skipped step still
 advances the step counter and so the bias corrections: the kernel's scalars
 are rounded on the host exactly as torch rounds its Python floats, which a
 device-side count (a device ``pow``) could not promise bit for bit.
+
+``ema_decay`` keeps an exponential moving average of the weights in one more
+arena-sized array that the same launch reads and writes
+(``pis_adamw_step_ema``): ``e += w_k (p_new - e)`` with ``w_k = 1 - d_k``,
+``d_k = min(ema_decay, (1 + k) / (10 + k))`` (``ema_warmup``) or ``ema_decay``,
+``k`` the optimizer's 1-based step count. A skipped step counts in ``k`` but
+does not move the average. ``averaged_weights()`` exchanges the CONTENTS of the
+parameter arena and the average (``pis_arena_exchange``), never pointers:
+parameter views, the engine's filter-job tables and a captured ``StepGraph`` all
+hold addresses. Data parallel needs no communication: every rank holds the same
+weights, hence the same average. Off by default; with ``ema_decay=None`` the
+launches are the ones above and no EMA state exists.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -34,15 +47,21 @@ from . import _hip
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2, grad_scale: float = 1.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         if lr < 0 or eps < 0 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameter")
         if max_grad_norm is not None and not max_grad_norm > 0:  # <= 0 and NaN
             raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+        if ema_decay is not None and not 0.0 < ema_decay < 1.0:  # NaN too
+            raise ValueError(f"ema_decay must be in (0, 1) or None, got {ema_decay!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = ema_decay
+        self.ema_warmup = bool(ema_warmup)
+        self._averaged = False  # inside averaged_weights(): the arenas' contents are exchanged
         self._flat = {}  # group index -> (arena tensor, m, v, offsets) when every param views one arena
 
     # ---- arena discovery ------------------------------------------------------
@@ -66,6 +85,8 @@ class AdamW(torch.optim.Optimizer):
         # adopt moments a previous (per-tensor or older) state may hold
         m = torch.zeros_like(arena)
         v = torch.zeros_like(arena)
+        # the average starts from the weights (padding included: the exchange moves whole arenas)
+        ema = arena.clone() if self.ema_decay is not None else None
         step = 0
         for p, o in zip(params, offs):
             s = self.state.get(p)
@@ -73,19 +94,28 @@ class AdamW(torch.optim.Optimizer):
                 m.narrow(0, o, p.numel()).copy_(s["exp_avg"].reshape(-1))
                 v.narrow(0, o, p.numel()).copy_(s["exp_avg_sq"].reshape(-1))
                 step = int(s.get("step", 0))
+            if ema is not None and s and "ema" in s:
+                ema.narrow(0, o, p.numel()).copy_(s["ema"].reshape(-1))
         for p, o in zip(params, offs):
             self.state[p] = {"step": torch.tensor(float(step)),
                              "exp_avg": m.narrow(0, o, p.numel()).view(p.shape) if p.is_contiguous()
                              else m.narrow(0, o, p.numel()),
                              "exp_avg_sq": v.narrow(0, o, p.numel()).view(p.shape) if p.is_contiguous()
                              else v.narrow(0, o, p.numel())}
+            if ema is not None:
+                self.state[p]["ema"] = ema.narrow(0, o, p.numel()).view(p.shape) if p.is_contiguous() \
+                    else ema.narrow(0, o, p.numel())
         st = {"key": key, "arena": arena, "m": m, "v": v, "offs": offs, "step": step}
+        if ema is not None:
+            st["ema"] = ema
         self._flat[gi] = st
         return st
 
     # ---- step -----------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None):
+        if self._averaged:
+            raise RuntimeError("AdamW.step inside averaged_weights(): the model holds the averaged weights")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -112,6 +142,8 @@ class AdamW(torch.optim.Optimizer):
             arena, m, v, offs = st["arena"], st["m"], st["v"], st["offs"]
             g_flat = self._grad_arena(params, offs, arena)
             stream = _hip.stream_handle()
+            ema = st.get("ema")
+            w = self.ema_weight(step) if ema is not None else None
             if self.norm_path:
                 if g_flat is None or not all(with_grad):
                     raise NotImplementedError(
@@ -123,11 +155,21 @@ class AdamW(torch.optim.Optimizer):
                           _hip.PIS_GRADNORM_SKIP_NONFINITE if self.skip_nonfinite else 0,
                           nb["sumsq"].data_ptr(), nb["record"].data_ptr(), nb["stats"].data_ptr(),
                           nb["ws"].data_ptr(), nb["ws"].numel(), stream)
+                if ema is not None:
+                    _hip.call("pis_adamw_step_ema", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(),
+                              v.data_ptr(), ema.data_ptr(), arena.numel(), lr, b1, b2, eps, wd, step_size,
+                              bc2_sqrt, self.grad_scale, w, nb["record"].data_ptr(), stream)
+                    continue
                 _hip.call("pis_adamw_step_clipped", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(),
                           v.data_ptr(), arena.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt,
                           self.grad_scale, nb["record"].data_ptr(), stream)
                 continue
             if g_flat is not None and all(with_grad):
+                if ema is not None:
+                    _hip.call("pis_adamw_step_ema", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(),
+                              v.data_ptr(), ema.data_ptr(), arena.numel(), lr, b1, b2, eps, wd, step_size,
+                              bc2_sqrt, self.grad_scale, w, 0, stream)
+                    continue
                 _hip.call("pis_adamw_step", arena.data_ptr(), g_flat.data_ptr(), m.data_ptr(), v.data_ptr(),
                           arena.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale, stream)
                 continue
@@ -137,9 +179,75 @@ class AdamW(torch.optim.Optimizer):
                 g = p.grad
                 if g.stride() != p.stride():
                     g = torch.empty_strided(p.shape, p.stride(), device=p.device).copy_(g)
+                if ema is not None:  # a parameter without .grad keeps its slice of the average
+                    _hip.call("pis_adamw_step_ema", p.data_ptr(), g.data_ptr(), m.data_ptr() + 4 * o,
+                              v.data_ptr() + 4 * o, ema.data_ptr() + 4 * o, p.numel(), lr, b1, b2, eps, wd,
+                              step_size, bc2_sqrt, self.grad_scale, w, 0, stream)
+                    continue
                 _hip.call("pis_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr() + 4 * o, v.data_ptr() + 4 * o,
                           p.numel(), lr, b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale, stream)
         return loss
+
+    # ---- exponential moving average of the weights -----------------------------
+    def ema_weight(self, step: int) -> float:
+        """The weight ``w_k = 1 - d_k`` of step number ``step`` (1-based, skipped steps counted), in
+        float64: ``d_k = min(ema_decay, (1 + k) / (10 + k))`` with ``ema_warmup``, else ``ema_decay``."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weight: the optimizer was built without ema_decay")
+        d = min(self.ema_decay, (1.0 + step) / (10.0 + step)) if self.ema_warmup else self.ema_decay
+        return 1.0 - d
+
+    def _ema_state(self, what: str):
+        if self.ema_decay is None:
+            raise RuntimeError(f"{what}: the optimizer was built without ema_decay")
+        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
+        if len(groups) != 1:
+            raise RuntimeError(f"{what}: one parameter group expected")
+        gi, group = groups[0]
+        _hip.require_cuda(group["params"][0], what)
+        st = self._flat_state(gi, group)
+        if st is None:
+            raise NotImplementedError("AdamW (MI355X) expects the parameters of one UNet (a single arena)")
+        return st
+
+    def ema_arena(self) -> torch.Tensor:
+        """The flat average, laid out like the parameter arena (created from the current weights, or
+        adopted from a loaded state, when no step has been taken yet). Inside ``averaged_weights()``
+        the contents are exchanged: this tensor then holds the raw weights."""
+        return self._ema_state("ema_arena")["ema"]
+
+    def ema_state_dict(self, model: torch.nn.Module) -> Dict[str, torch.Tensor]:
+        """``model.state_dict()``'s keys and shapes with the averaged values, as fresh tensors (entries
+        that do not live in the parameter arena are copied as they are)."""
+        st = self._ema_state("ema_state_dict")
+        arena = st["arena"]
+        src = arena if self._averaged else st["ema"]  # exchanged: the arena holds the average
+        base, nbytes = self._storage(arena)
+        out = {}
+        for k, t in model.state_dict().items():
+            if t.is_cuda and self._storage(t) == (base, nbytes) and t.dtype == torch.float32:
+                out[k] = torch.as_strided(src, t.shape, t.stride(), (t.data_ptr() - base) // 4).clone()
+            else:
+                out[k] = t.clone()
+        return out
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the ``with`` body the model holds the averaged weights: one ``pis_arena_exchange``
+        of the parameter arena with the average on entry, one on exit (also when the body raises).
+        ``step()`` and a nested entry raise inside it. No host synchronisation: the launches queue on
+        the current stream. Not to be issued between the begin and the end of a graph capture."""
+        st = self._ema_state("averaged_weights")
+        if self._averaged:
+            raise RuntimeError("averaged_weights: already inside averaged_weights()")
+        arena, ema = st["arena"], st["ema"]
+        _hip.call("pis_arena_exchange", arena.data_ptr(), ema.data_ptr(), arena.numel(), _hip.stream_handle())
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            _hip.call("pis_arena_exchange", arena.data_ptr(), ema.data_ptr(), arena.numel(), _hip.stream_handle())
+            self._averaged = False
 
     # ---- gradient norm, clipping, step guard -----------------------------------
     @property

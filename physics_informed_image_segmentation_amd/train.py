@@ -355,7 +355,11 @@ def validate(model, dataloader, criterion, device, return_components: bool = Fal
 def train_stage(model, train_loader, val_loader, criterion, optimizer, device, num_epochs: int,
                 stage_name: str, early_stopping: Optional[EarlyStopping] = None, verbose: bool = True,
                 csv_path: Optional[Path] = None) -> Tuple[Dict, int, List[Dict]]:
-    """Epoch loop with best-val-Dice tracking, CSV and early stopping (src/train.py:289-391)."""
+    """Epoch loop with best-val-Dice tracking, CSV and early stopping (src/train.py:289-391). With
+    an optimizer whose ``ema_decay`` is set, validation runs inside ``optimizer.averaged_weights()``:
+    the epoch's validation figures, the best-Dice tracking and early stopping refer to the averaged
+    weights; the training figures and every key stay as they are."""
+    ema_on = getattr(optimizer, "ema_decay", None) is not None
     best_dice, best_epoch, best = 0.0, 0, {}
     history: List[Dict] = []
     is_main = not (torch.distributed.is_available() and torch.distributed.is_initialized()) or \
@@ -367,7 +371,11 @@ def train_stage(model, train_loader, val_loader, criterion, optimizer, device, n
                 obj.set_epoch(epoch)
         tr = train_epoch(model, train_loader, criterion, optimizer, device, return_components=True,
                          compute_metrics=True)
-        va = validate(model, val_loader, criterion, device, return_components=True, compute_metrics=True)
+        if ema_on:
+            with optimizer.averaged_weights():
+                va = validate(model, val_loader, criterion, device, return_components=True, compute_metrics=True)
+        else:
+            va = validate(model, val_loader, criterion, device, return_components=True, compute_metrics=True)
         if va["dice_score"] > best_dice:
             best_dice, best_epoch, best = va["dice_score"], epoch, {"train": tr, "val": va}
         row = {"epoch": epoch}
@@ -484,7 +492,8 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           early_stopping_patience: int = 10, train_fraction: Optional[float] = None, seed: int = 42,
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
           num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
-          augment=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+          augment=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+          ema_decay: Optional[float] = None, ema_warmup: bool = True):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -503,7 +512,14 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     ``device_data=False``), with ``augment`` ("flip" / "d4" / "affine" or a ``dataset.AffineAugment``) on its training loader; a cache that
     does not fit falls back to the ``DataLoader`` path. ``max_grad_norm`` (global L2 gradient clipping)
     and ``skip_nonfinite`` (skip a step whose gradient norm is Inf or NaN) go to both stages'
-    ``AdamW``; off by default."""
+    ``AdamW``; off by default. ``ema_decay`` (with ``ema_warmup``) also goes to both stages' ``AdamW``:
+    an exponential moving average of the weights kept inside the AdamW launch, each stage's average
+    starting from the model's weights at that stage's start. Validation, best-Dice tracking, early
+    stopping and the final test-set evaluation then run on the averaged weights, and next to the
+    unchanged unet_baseline.pth / unet_pde_regularized.pth rank 0 writes unet_baseline_ema.pth /
+    unet_pde_regularized_ema.pth (plain state dicts; the Stage-I comparison model loads the _ema
+    file). Data parallel needs no communication for it: all ranks hold identical weights, hence
+    identical averages."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     rank, local_rank, world = init_from_env()
@@ -567,10 +583,24 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
 
     def run(criterion, lr, epochs, name, csv_path):
         opt = AdamW(model.parameters(), lr=lr, weight_decay=1e-5, grad_scale=grad_scale,
-                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+                    ema_warmup=ema_warmup)
+        opts.append(opt)
         stopper = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
         return train_stage(model, train_loader, val_loader, criterion, opt, device, num_epochs=epochs,
                            stage_name=name, early_stopping=stopper, verbose=True, csv_path=csv_path)
+
+    opts: List[AdamW] = []  # the stages' optimizers; the last one holds the final average
+
+    def save_ema(path):
+        """The stage's averaged weights as a plain state dict next to the raw ones (rank 0)."""
+        if ema_decay is None:
+            return None
+        ema_path = path.with_name(path.stem + "_ema.pth")
+        if is_main:
+            torch.save(opts[-1].ema_state_dict(model), ema_path)
+        say(f"Averaged (EMA) weights saved to: {ema_path}")
+        return ema_path
 
     def pde_loss():
         return DiceBCEPDELoss(dice_weight=0.5, bce_weight=0.5, pde_weight=pde_weight,
@@ -602,6 +632,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         models_dir.mkdir(parents=True, exist_ok=True)
         torch.save(model.state_dict(), stage1_path)
     say(f"Stage I model saved to: {stage1_path}")
+    stage1_ema_path = save_ema(stage1_path)
     if use_two_stage:
         say("\n" + "=" * 70 + "\nSTAGE II: PDE-CONSTRAINED FINE-TUNING\n" + "=" * 70)
         describe_pde()
@@ -632,21 +663,24 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     if is_main:
         torch.save(model.state_dict(), final_path)
     say(f"Model saved to: {final_path}")
+    save_ema(final_path)
 
     # ---- test-set evaluation (src/train.py:848-911), rank 0 ----
     say("\n" + "=" * 70 + "\nTEST SET EVALUATION\n" + "=" * 70)
     if is_main and test_json.exists() and test_dir.exists():
         from .evaluate import evaluate_on_test_set
         name = "PDE-Constrained (Stage II)" if use_two_stage else "Single-Stage PDE-Constrained"
-        m = evaluate_on_test_set(model, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
-                                 model_name=name, device_cache=device_cache)
+        import contextlib
+        with opts[-1].averaged_weights() if ema_decay is not None else contextlib.nullcontext():
+            m = evaluate_on_test_set(model, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
+                                     model_name=name, device_cache=device_cache)
         tag = "stage2" if use_two_stage else "single_stage"
         save_test_metrics(m, out_dir / f"test_metrics_{tag}_{stamp}{frac}", model_name=name)
         result["test"] = m
         if use_two_stage:
             say("\n" + "=" * 70 + "\nEVALUATING STAGE I MODEL ON TEST SET\n" + "=" * 70)
             stage1 = UNet(in_channels=1, out_channels=1, base_channels=64)
-            stage1.load_state_dict(torch.load(stage1_path, map_location="cpu", weights_only=True))
+            stage1.load_state_dict(torch.load(stage1_ema_path or stage1_path, map_location="cpu", weights_only=True))
             stage1 = stage1.to(device)
             m1 = evaluate_on_test_set(stage1, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
                                       model_name="Baseline (Stage I)", device_cache=device_cache)

@@ -47,11 +47,18 @@ def parse_args(argv=None):
                     help="clip the global L2 norm of the gradients to FLOAT inside the fused AdamW step (default: off)")
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="skip an optimizer step whose gradient norm is Inf or NaN (default: off)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                    help="keep an exponential moving average of the weights with decay FLOAT in (0, 1) inside the "
+                         "fused AdamW step; validation, early stopping and evaluation use it (default: off)")
+    ap.add_argument("--no-ema-warmup", action="store_true",
+                    help="use --ema-decay from the first step instead of min(decay, (1 + k) / (10 + k))")
     args = ap.parse_args(argv)
     if args.augment and not args.device_cache:
         ap.error("--augment needs --device-cache")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
         ap.error("--clip-grad-norm must be positive")
+    if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
+        ap.error("--ema-decay must be in (0, 1)")
     return args
 
 
@@ -79,7 +86,8 @@ def main(argv=None):
                                  output_dir=Path(args.output_dir) if args.output_dir else None,
                                  num_workers=args.num_workers, boundary_metrics=not args.no_boundary_metrics,
                                  device_cache=args.device_cache, augment=args.augment,
-                                 max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                                 max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
+                                 ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
         print(f"\nAblation {name} complete!\nResults: {res['results_json']}\nSummary: {res['summary_csv']}")
         out[name] = res
     print("\n" + "=" * 70 + "\nALL ABLATION STUDIES COMPLETE\n" + "=" * 70)
