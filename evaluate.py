@@ -35,6 +35,13 @@ def parse_args(argv=None):
     ap.add_argument("--augment", choices=["flip", "d4", "affine"], default=None,
                     help="accepted so main.py's data flags can be passed unchanged; it applies to training "
                          "loaders only, and evaluation has none")
+    ap.add_argument("--object-metrics", action="store_true",
+                    help="also report object-level metrics: detection F1 at IoU > 0.5, Aggregated Jaccard Index "
+                         "and the object count error (connected components on the GPU)")
+    ap.add_argument("--connectivity", type=int, choices=[4, 8], default=8,
+                    help="pixel connectivity of an object for --object-metrics (default: 8)")
+    ap.add_argument("--min-object-area", type=int, default=0, metavar="N",
+                    help="drop predicted objects below N pixels before --object-metrics (default: 0)")
     return ap.parse_args(argv)
 
 
@@ -51,6 +58,8 @@ def main(argv=None):
                   batch_size=args.batch_size, threshold=args.threshold, output_dir=Path(args.output_dir))
     if args.device_cache:
         common["device_cache"] = True
+    if args.object_metrics:
+        common.update(object_metrics=True, connectivity=args.connectivity, min_object_area=args.min_object_area)
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

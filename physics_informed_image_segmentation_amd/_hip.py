@@ -105,6 +105,8 @@ _SIGNATURES = {
     "pis_synth_discs": ([P, P, I, ctypes.c_uint64, P, P, P, I, I, I, P, Z, P], c_int),
     "pis_boundary_ws": ([I, I, I], c_size_t),
     "pis_boundary_metrics": ([P, P, I, I, I, c_float, I, P, P, P, P, Z, P], c_int),
+    "pis_objects_ws": ([I, I, I], c_size_t),
+    "pis_object_metrics": ([P, P, I, I, I, c_float, I, I, P, P, P, P, Z, P], c_int),
     "pis_cache_batch": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
     "pis_cache_batch_affine": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
 }

@@ -29,6 +29,11 @@
   the device entry points; ``compute_boundary_f1_batch``, ``compute_boundary_f1`` and
   ``compute_hausdorff_distance`` take ``backend="auto" | "host" | "device"`` ("auto": device when
   both tensors are CUDA tensors). The host functions are unchanged and are the tests' oracle.
+* Object-level metrics (no reference counterpart): connected components of prediction and target,
+  detection F1 at IoU > 0.5 / 0.75 and the Aggregated Jaccard Index, from eight exact integer
+  counters per sample. ``object_counts`` / ``label_components`` run on the GPU for CUDA tensors
+  (csrc/components.hip, pis_object_metrics) and by scipy.ndimage.label + numpy otherwise; the two
+  agree with == (tests/test_objects_gpu.py). ``evaluate_model(object_metrics=True)`` adds them.
 """
 from __future__ import annotations
 
@@ -228,15 +233,195 @@ def compute_hausdorff_distance(predictions: torch.Tensor, targets: torch.Tensor,
     return float(max(directed_hausdorff(pc, tc)[0], directed_hausdorff(tc, pc)[0]))
 
 
+# ----------------------------------------------------------------------------
+# Object-level metrics: components, detection F1, Aggregated Jaccard Index (csrc/components.hip)
+# ----------------------------------------------------------------------------
+# Definitions (include/pis_capi.h). An object is a connected component of the
+# foreground (prediction: p > threshold, NaN is background; target: t > 0) under ``connectivity``
+# (4 or 8); the objects of an image are numbered 1..n in row-major order of their first pixel.
+# Predicted objects below ``min_area`` pixels are removed before the numbering and everything
+# else; targets are never filtered. The eight counters of a sample are
+#   n_p, n_t, tp50 (pairs with 3 I > A_p + A_t), tp75 (7 I > 3 (A_p + A_t)), aji_inter, aji_union,
+#   area_p (pixels of the kept predicted objects), removed (predicted objects dropped)
+# with AJI in the HoVer-Net form: every true object takes the overlapping prediction of largest
+# I / U (exact fractions, ties to the smaller object number); its I and U are added, the
+# prediction is marked used; a true object without overlap adds its area to the union, and so
+# does every kept prediction that is never used. All integers: the device path equals the host
+# path (scipy.ndimage.label + numpy) with ==.
+
+OBJ_NP, OBJ_NT, OBJ_TP50, OBJ_TP75, OBJ_AJI_INTER, OBJ_AJI_UNION, OBJ_AREA_P, OBJ_REMOVED = range(8)
+_EIGHT = ndimage.generate_binary_structure(2, 2)
+
+
+def _check_objects(connectivity: int, min_area: int) -> None:
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 0:
+        raise ValueError(f"min_area must be an integer >= 0, got {min_area!r}")
+
+
+def _label_np(fg: np.ndarray, connectivity: int, min_area: int) -> Tuple[np.ndarray, int, int]:
+    """Canonical label map of a boolean (H, W) image: (labels int32, objects kept, objects removed)."""
+    lab, n = ndimage.label(fg, structure=_EIGHT if connectivity == 8 else _FOUR)
+    flat = lab.ravel()
+    idx = np.flatnonzero(flat)
+    ids, first = np.unique(flat[idx], return_index=True)  # the first pixel of every component
+    keep = np.bincount(flat, minlength=n + 1)[ids] >= min_area
+    ids, first = ids[keep], idx[first[keep]]
+    number = np.zeros(n + 1, np.int32)
+    number[ids[np.argsort(first, kind="stable")]] = np.arange(1, ids.size + 1, dtype=np.int32)
+    return number[lab], int(ids.size), int(n - ids.size)
+
+
+def _object_counts_np(lp: np.ndarray, n_p: int, removed: int, lt: np.ndarray, n_t: int) -> np.ndarray:
+    """The eight counters of one sample from its two canonical label maps."""
+    a_p = np.bincount(lp.ravel(), minlength=n_p + 1).astype(np.int64)
+    a_t = np.bincount(lt.ravel(), minlength=n_t + 1).astype(np.int64)
+    both = (lp > 0) & (lt > 0)
+    # pairs sorted by true object, then by predicted object
+    code, inter = np.unique(lt[both].astype(np.int64) * (n_p + 1) + lp[both], return_counts=True)
+    tt, pp = code // (n_p + 1), code % (n_p + 1)
+    inter = inter.astype(np.int64)
+    s = a_p[pp] + a_t[tt]
+    union = s - inter
+    tp50, tp75 = int((3 * inter > s).sum()), int((7 * inter > 3 * s).sum())
+    used = np.zeros(n_p + 1, bool)
+    matched = np.zeros(n_t + 1, bool)
+    aji_i = aji_u = 0
+    _, start, size = np.unique(tt, return_index=True, return_counts=True)
+    for b, k in zip(start.tolist(), size.tolist()):
+        best = b
+        for e in range(b + 1, b + k):  # ascending object number: '>' leaves ties with the smaller
+            if int(inter[e]) * int(union[best]) > int(inter[best]) * int(union[e]):
+                best = e
+        aji_i += int(inter[best])
+        aji_u += int(union[best])
+        used[pp[best]] = True
+        matched[tt[best]] = True
+    aji_u += int(a_t[1:][~matched[1:]].sum()) + int(a_p[1:][~used[1:]].sum())
+    return np.array([n_p, n_t, tp50, tp75, aji_i, aji_u, int(a_p[1:].sum()), removed], np.int64)
+
+
+def _objects_host(predictions: torch.Tensor, targets: torch.Tensor, threshold: float, connectivity: int,
+                  min_area: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(counts (B, 8) int64, labels_p, labels_t (B, H, W) int32) by scipy and numpy."""
+    p, t = _bhw(predictions).cpu().numpy(), _bhw(targets).cpu().numpy()
+    if p.shape != t.shape:
+        raise ValueError(f"predictions {p.shape} and targets {t.shape} differ")
+    counts, lps, lts = [], [], []
+    with np.errstate(invalid="ignore"):
+        fp, ft = p > threshold, t > 0
+    for i in range(p.shape[0]):
+        lp, n_p, removed = _label_np(fp[i], connectivity, min_area)
+        lt, n_t, _ = _label_np(ft[i], connectivity, 0)
+        counts.append(_object_counts_np(lp, n_p, removed, lt, n_t))
+        lps.append(lp)
+        lts.append(lt)
+    return np.stack(counts), np.stack(lps), np.stack(lts)
+
+
+def _objects_device(predictions: torch.Tensor, targets: torch.Tensor, threshold: float, connectivity: int,
+                    min_area: int, maps: bool = False, ws: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One pis_object_metrics call on the current stream: (counts, labels_p, labels_t). ``ws``: a
+    uint8 CUDA tensor of at least pis_objects_ws bytes to use as the workspace (its contents do not
+    matter); allocated from the caching allocator when None."""
+    p, t = _bhw(predictions), _bhw(targets)
+    _hip.require_cuda(p, "object_counts")
+    _hip.require_cuda(t, "object_counts")
+    if p.shape != t.shape or p.device != t.device:
+        raise ValueError(f"predictions {tuple(p.shape)} on {p.device} and targets {tuple(t.shape)} on {t.device} differ")
+    B, H, W = p.shape
+    with torch.cuda.device(p.device):
+        nbytes = _hip.lib().pis_objects_ws(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"object_counts: unsupported shape B={B} H={H} W={W} (B >= 1, 1 <= H, W <= 4096)")
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+        counts = torch.empty((B, 8), dtype=torch.int64, device=p.device)
+        lp = torch.empty((B, H, W), dtype=torch.int32, device=p.device) if maps else None
+        lt = torch.empty((B, H, W), dtype=torch.int32, device=p.device) if maps else None
+        _hip.call("pis_object_metrics", _hip.ptr(p), _hip.ptr(t), B, H, W, ctypes.c_float(float(threshold)),
+                  int(connectivity), int(min_area), _hip.ptr(counts), _hip.ptr(lp), _hip.ptr(lt), _hip.ptr(ws),
+                  ws.numel(), _hip.stream_handle(p.device))
+    return counts, lp, lt
+
+
+def object_counts(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5, connectivity: int = 8,
+                  min_area: int = 0, backend: str = "auto") -> torch.Tensor:
+    """(B, 8) int64 (n_p, n_t, tp50, tp75, aji_inter, aji_union, area_p, removed) per sample. CUDA
+    tensors: on their device, one pis_object_metrics call, no host synchronisation. CPU tensors
+    (and ``backend="host"``): scipy.ndimage.label + numpy, a CPU tensor; the two agree exactly."""
+    _check_objects(connectivity, min_area)
+    if _use_device(backend, predictions, targets):
+        return _objects_device(predictions, targets, threshold, connectivity, int(min_area))[0]
+    return torch.from_numpy(_objects_host(predictions, targets, threshold, connectivity, int(min_area))[0])
+
+
+def label_components(masks: torch.Tensor, threshold: float = 0.0, connectivity: int = 8, min_area: int = 0,
+                     backend: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Objects of every (H, W) image of a batch (foreground: mask > threshold): (labels int32
+    (B, H, W), n int64 (B,)), numbered 1..n in row-major order of their first pixel; 0 is the
+    background and every object below ``min_area`` pixels."""
+    _check_objects(connectivity, min_area)
+    if _use_device(backend, masks, masks):
+        counts, lp, _ = _objects_device(masks, masks, threshold, connectivity, int(min_area), maps=True)
+        return lp, counts[:, OBJ_NP].contiguous()
+    with np.errstate(invalid="ignore"):
+        fg = _bhw(masks).cpu().numpy() > threshold
+    res = [_label_np(m, connectivity, int(min_area)) for m in fg]
+    return (torch.from_numpy(np.stack([r[0] for r in res])),
+            torch.tensor([r[1] for r in res], dtype=torch.int64))
+
+
+def _object_f1_from_counts(counts: torch.Tensor, iou: float = 0.5) -> torch.Tensor:
+    """2 tp / (n_p + n_t) as float64 on the counters' device; NaN where there is no object at all."""
+    if iou not in (0.5, 0.75):
+        raise ValueError(f"iou must be 0.5 or 0.75, got {iou!r}")
+    c = counts.to(torch.float64)
+    den = c[:, OBJ_NP] + c[:, OBJ_NT]
+    f1 = 2.0 * c[:, OBJ_TP50 if iou == 0.5 else OBJ_TP75] / den
+    return torch.where(den > 0, f1, torch.full_like(f1, float("nan")))
+
+
+def _aji_from_counts(counts: torch.Tensor) -> torch.Tensor:
+    c = counts.to(torch.float64)
+    aji = c[:, OBJ_AJI_INTER] / c[:, OBJ_AJI_UNION]
+    return torch.where(c[:, OBJ_NP] + c[:, OBJ_NT] > 0, aji, torch.full_like(aji, float("nan")))
+
+
+def compute_object_f1_batch(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
+                            connectivity: int = 8, min_area: int = 0, iou: float = 0.5,
+                            backend: str = "auto") -> torch.Tensor:
+    """Per-sample detection F1 at IoU > ``iou`` (0.5 or 0.75): 2 tp / (n_p + n_t), float64 on the
+    counters' device; NaN for a sample with no predicted and no true object."""
+    if iou not in (0.5, 0.75):
+        raise ValueError(f"iou must be 0.5 or 0.75, got {iou!r}")
+    return _object_f1_from_counts(object_counts(predictions, targets, threshold, connectivity, min_area, backend), iou)
+
+
+def compute_aji_batch(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
+                      connectivity: int = 8, min_area: int = 0, backend: str = "auto") -> torch.Tensor:
+    """Per-sample Aggregated Jaccard Index aji_inter / aji_union, float64 on the counters' device;
+    NaN for a sample with no predicted and no true object."""
+    return _aji_from_counts(object_counts(predictions, targets, threshold, connectivity, min_area, backend))
+
+
 @torch.no_grad()
 def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_metrics: bool = True,
-                   boundary_backend: str = "auto") -> Dict[str, np.ndarray]:
+                   boundary_backend: str = "auto", object_metrics: bool = False, connectivity: int = 8,
+                   min_object_area: int = 0, object_backend: str = "auto") -> Dict[str, np.ndarray]:
     """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
     (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
     ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
-    "host" or "device", as ``compute_boundary_f1_batch``)."""
+    "host" or "device", as ``compute_boundary_f1_batch``). ``object_metrics=True`` adds
+    ``object_f1_scores`` (IoU > 0.5), ``aji_scores`` and ``object_count_errors`` (n_p - n_t) from
+    one ``object_counts`` call and one device->host copy per batch."""
     model.eval()
+    if object_metrics:
+        _check_objects(connectivity, min_object_area)
     dice, iou, bf1, hd = [], [], [], []
+    of1, aji, cerr = [], [], []
     for images, masks in dataloader:
         images, masks = images.to(device, non_blocking=True), masks.to(device, non_blocking=True)
         outputs = model(images)
@@ -257,10 +442,21 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
                 h = compute_hausdorff_distance(outputs[i:i + 1], masks[i:i + 1], threshold=threshold,
                                                backend="host")
                 hd.append(h if np.isfinite(h) else np.nan)
+        if object_metrics:
+            counts = object_counts(outputs, masks, threshold, connectivity, min_object_area, object_backend)
+            three = torch.stack([_object_f1_from_counts(counts, 0.5), _aji_from_counts(counts),
+                                 (counts[:, OBJ_NP] - counts[:, OBJ_NT]).to(torch.float64)]).cpu().numpy()
+            of1.extend(three[0].tolist())
+            aji.extend(three[1].tolist())
+            cerr.extend(three[2].tolist())
     out = {"dice_scores": np.array(dice), "iou_scores": np.array(iou)}
     if boundary_metrics:
         out["boundary_f1_scores"] = np.array(bf1)
         out["hausdorff_distances"] = np.array(hd)
+    if object_metrics:
+        out["object_f1_scores"] = np.array(of1)
+        out["aji_scores"] = np.array(aji)
+        out["object_count_errors"] = np.array(cerr)
     return out
 
 
@@ -317,11 +513,12 @@ def format_metric_report(metrics: Dict[str, np.ndarray], model_name: str = "Mode
 
 
 def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8, threshold: float = 0.5,
-                         model_name: str = "Model", device_cache: bool = False) -> Dict[str, np.ndarray]:
+                         model_name: str = "Model", device_cache: bool = False, object_metrics: bool = False,
+                         connectivity: int = 8, min_object_area: int = 0) -> Dict[str, np.ndarray]:
     """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
     ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
     (``dataset.DeviceCachedLoader``) instead of ``DataLoader`` workers; a set that does not fit
-    falls back to them."""
+    falls back to them. ``object_metrics=True`` adds the object-level arrays of ``evaluate_model``."""
     from torch.utils.data import DataLoader
 
     from .dataset import CellSegmentationDataset, DeviceCachedLoader
@@ -340,7 +537,8 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
         loader = DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=2,
                             pin_memory=torch.cuda.is_available())
     print(f"Test samples: {len(ds)}")
-    metrics = evaluate_model(model, loader, device, threshold=threshold)
+    metrics = evaluate_model(model, loader, device, threshold=threshold, object_metrics=object_metrics,
+                             connectivity=connectivity, min_object_area=min_object_area)
     print(format_metric_report(metrics, model_name=model_name))
     return metrics
 
@@ -349,4 +547,5 @@ __all__ = ["compute_iou", "compute_iou_batch", "extract_boundaries", "compute_bo
            "compute_boundary_f1_batch", "compute_hausdorff_distance", "boundary_counts",
            "extract_boundaries_device", "compute_hausdorff_distance_batch", "evaluate_model",
            "compute_dice_score_batch", "compute_statistics", "compare_models_statistically",
-           "format_metric_report", "evaluate_on_test_set"]
+           "format_metric_report", "evaluate_on_test_set", "object_counts", "label_components",
+           "compute_object_f1_batch", "compute_aji_batch"]

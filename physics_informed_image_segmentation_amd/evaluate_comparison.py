@@ -23,6 +23,11 @@ from .evaluate import compare_models_statistically, compute_statistics, evaluate
 from .unet import UNet
 
 METRIC_KEYS = ("dice_scores", "iou_scores", "boundary_f1_scores", "hausdorff_distances")
+# appended only when the object-level metrics are switched on (evaluate.py: evaluate_model)
+OBJECT_METRIC_KEYS = ("object_f1_scores", "aji_scores", "object_count_errors")
+_COLUMNS = {"dice_scores": "dice", "iou_scores": "iou", "boundary_f1_scores": "boundary_f1",
+            "hausdorff_distances": "hausdorff", "object_f1_scores": "object_f1", "aji_scores": "aji",
+            "object_count_errors": "object_count_error"}
 _DEFAULT_OUT = Path(__file__).resolve().parent.parent / "output"
 
 
@@ -73,26 +78,28 @@ def _print_comparison(results: Dict[str, Dict[str, float]]):
 
 def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_dir: Path, test_json: Path,
                          device: torch.device, batch_size: int = 8, threshold: float = 0.5,
-                         output_dir: Optional[Path] = None, device_cache: bool = False) -> Dict:
+                         output_dir: Optional[Path] = None, device_cache: bool = False,
+                         object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0) -> Dict:
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
+    obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
     print("=" * 70 + "\nMODEL EVALUATION AND STATISTICAL COMPARISON\n" + "=" * 70)
     print("\nLoading models...")
     base = evaluate_on_test_set(load_model(baseline_model_path, device), test_dir, test_json, device,
                                 batch_size=batch_size, threshold=threshold, model_name="Baseline (Unconstrained)",
-                                device_cache=device_cache)
+                                device_cache=device_cache, **obj)
     pde = evaluate_on_test_set(load_model(pde_model_path, device), test_dir, test_json, device,
                                batch_size=batch_size, threshold=threshold, model_name="PDE-Constrained",
-                               device_cache=device_cache)
+                               device_cache=device_cache, **obj)
     print("\n" + "=" * 70 + "\nSTATISTICAL COMPARISON\n" + "=" * 70)
     cmp = compare_models_statistically(base, pde, alpha=0.05)
     _print_comparison(cmp)
 
     ts = datetime.now().strftime("%Y%m%d_%H%M%S")
     per_image = {"image_id": range(len(base["dice_scores"]))}
-    for key, col in (("dice_scores", "dice"), ("iou_scores", "iou"), ("boundary_f1_scores", "boundary_f1"),
-                     ("hausdorff_distances", "hausdorff")):
+    for key in METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ()):
+        col = _COLUMNS[key]
         per_image[f"baseline_{col}"] = base[key]
         per_image[f"pde_{col}"] = pde[key]
     results_csv = out_dir / f"evaluation_results_{ts}.csv"
@@ -119,19 +126,22 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
 
 def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: List[Path], test_dir: Path,
                              test_json: Path, device: torch.device, batch_size: int = 8, threshold: float = 0.5,
-                             output_dir: Optional[Path] = None, device_cache: bool = False) -> Dict:
+                             output_dir: Optional[Path] = None, device_cache: bool = False,
+                             object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0) -> Dict:
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
+    obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
+    metric_keys = METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
     print("=" * 70 + "\nREPEATED EXPERIMENTS EVALUATION\n" + "=" * 70)
     print(f"Number of runs: {len(baseline_model_paths)}")
-    pooled = {"baseline": {k: [] for k in METRIC_KEYS}, "pde": {k: [] for k in METRIC_KEYS}}
+    pooled = {"baseline": {k: [] for k in metric_keys}, "pde": {k: [] for k in metric_keys}}
     for i, (bp, pp) in enumerate(zip(baseline_model_paths, pde_model_paths)):
         print(f"\n{'=' * 70}\nRun {i + 1}/{len(baseline_model_paths)}\n{'=' * 70}")
         for tag, path, label in (("baseline", bp, f"Baseline Run {i + 1}"), ("pde", pp, f"PDE-Constrained Run {i + 1}")):
             m = evaluate_on_test_set(load_model(path, device), test_dir, test_json, device, batch_size=batch_size,
-                                     threshold=threshold, model_name=label, device_cache=device_cache)
-            for k in METRIC_KEYS:
+                                     threshold=threshold, model_name=label, device_cache=device_cache, **obj)
+            for k in metric_keys:
                 pooled[tag][k].extend(m[k])
     base = {k: np.array(v) for k, v in pooled["baseline"].items()}
     pde = {k: np.array(v) for k, v in pooled["pde"].items()}
@@ -148,7 +158,7 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
             print(f"  Improvement: {r['improvement']:+.4f}")
         print(f"  Significant: {'Yes' if r['significant'] else 'No'} (p={r['t_pvalue']:.4f})")
     rows = []
-    for name in METRIC_KEYS:
+    for name in metric_keys:
         for tag, arrs in (("baseline", base), ("pde", pde)):
             st = compute_statistics(arrs[name])
             rows.append({"metric": name, "model": tag, "mean": st["mean"], "std": st["std"], "count": st["count"]})
@@ -158,4 +168,5 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
     return {"baseline_metrics": base, "pde_metrics": pde, "comparison_results": cmp, "aggregated_csv": aggregated_csv}
 
 
-__all__ = ["make_json_serializable", "load_model", "evaluate_and_compare", "run_repeated_evaluations"]
+__all__ = ["METRIC_KEYS", "OBJECT_METRIC_KEYS", "make_json_serializable", "load_model", "evaluate_and_compare",
+           "run_repeated_evaluations"]
