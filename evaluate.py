@@ -13,6 +13,13 @@ from pathlib import Path
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def _calibration_bins(text):
+    n = int(text)
+    if not 1 <= n <= 1024 or n & (n - 1):
+        raise argparse.ArgumentTypeError(f"{text}: a power of two in 1..1024 is needed")
+    return n
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Evaluate and compare segmentation models")
     ap.add_argument("--baseline", type=str, required=True,
@@ -42,6 +49,12 @@ def parse_args(argv=None):
                     help="pixel connectivity of an object for --object-metrics (default: 8)")
     ap.add_argument("--min-object-area", type=int, default=0, metavar="N",
                     help="drop predicted objects below N pixels before --object-metrics (default: 0)")
+    ap.add_argument("--probability-metrics", action="store_true",
+                    help="also report probability-level metrics: AUROC, average precision, ECE, Brier score and the "
+                         "per-image best threshold; writes the pooled threshold sweep and reliability table per model")
+    ap.add_argument("--calibration-bins", type=_calibration_bins, default=16, metavar="N",
+                    help="confidence bins of the ECE and the reliability table for --probability-metrics: a power "
+                         "of two up to 1024 (default: 16)")
     return ap.parse_args(argv)
 
 
@@ -60,6 +73,8 @@ def main(argv=None):
         common["device_cache"] = True
     if args.object_metrics:
         common.update(object_metrics=True, connectivity=args.connectivity, min_object_area=args.min_object_area)
+    if args.probability_metrics:
+        common.update(probability_metrics=True, calibration_bins=args.calibration_bins)
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

@@ -226,7 +226,14 @@ int pis_version(void);
                                    equal to 0 (both about 1.1e-6 from float64). The key must not
                                    change between a pis_conv3x3_filter(s) / pis_conv3x3_bwd_prep and the
                                    pis_conv3x3_dgrad_ex that consumes it (the latter is checked) */
-#define PIS_TUNE_NKEYS 52
+#define PIS_TUNE_PROB_VARIANT 52 /* pis_probability_table (csrc/probability.hip), a bit set; every form gives the same
+                                    integers. 0 (default, the fastest on a constant field): every bin through LDS
+                                    atomics, two histograms per block, equal neighbouring pixels of a lane merged
+                                    into one add. 1: the two end bins counted per wave by ballot + popcount instead
+                                    (+10 %); 2: four histograms per block (equal); 4: one LDS atomic per pixel,
+                                    no merging (+15-25 % on constant and saturated fields). Measured in
+                                    profiles/probability_metrics.txt by tools/bench_probability.py */
+#define PIS_TUNE_NKEYS 53
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -636,6 +643,29 @@ size_t pis_objects_ws(int B, int H, int W);
 int pis_object_metrics(const float* p, const float* t, int B, int H, int W, float thr,
                        int connectivity, int min_area, int64_t* counts, int32_t* labels_p,
                        int32_t* labels_t, void* ws, size_t ws_bytes, pis_stream_t stream);
+
+/* ---- probability-level table of a batch: the one integer table the threshold sweep, AUROC,
+ * average precision, ECE and Brier score derive from (no reference counterpart;
+ * evaluate.py:probability_table), exact ----
+ * p: probabilities, t: masks, both (B, H, W) fp32, 4-byte aligned. Per pixel, every float step exact:
+ *   x   = p * 65536.0f
+ *   q   = clamp(ceil(x), 0, 65536) as an integer; NaN gives 0 (and counts in n_nan), -Inf and
+ *         negatives give 0, values above 1 and +Inf give 65536
+ *   bin = (q + 63) >> 6, in 0..PIS_PROB_BINS (= ceil(p * 1024) clamped; bin 0 holds q = 0 only), so
+ *         that p > j / 1024 holds exactly when bin > j, for every float p and j = 0..1023
+ *   cls = t > 0.5f (the target test of the loss kernel's counters; a NaN target is class 0)
+ *   table[b][cls][bin] = { count, sum of q }                       int64 (B, 2, 1025, 2)
+ *   extra[b] = { sum of q^2 over class 0, sum of q^2 over class 1, n_nan, 0 }
+ * All exact integers (count <= 2^24, sum of q <= 2^40, sum of q^2 <= 2^56), independent of launch
+ * order and bitwise reproducible. B >= 1, 1 <= H, W <= 4096; anything else and a NULL pointer are
+ * PIS_ERR_ARG, a workspace below pis_probability_ws(B, H, W) bytes PIS_ERR_WORKSPACE
+ * (pis_probability_ws is 0 for an unsupported shape). Two launches on `stream`, no host
+ * synchronisation, no state in ws between calls. */
+#define PIS_PROB_BINS 1024
+#define PIS_PROB_QBITS 16
+size_t pis_probability_ws(int B, int H, int W);
+int pis_probability_table(const float* p, const float* t, int B, int H, int W, int64_t* table,
+                          int64_t* extra, void* ws, size_t ws_bytes, pis_stream_t stream);
 
 /* ---- batches from a device-resident dataset cache (no reference counterpart: replaces the
  * DataLoader workers + host-to-device copies around src/dataset.py:55-84 once the samples have been

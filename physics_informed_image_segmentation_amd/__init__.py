@@ -12,11 +12,14 @@ __version__ = "0.2.0"
 
 from .dataset import (AffineAugment, CellSegmentationDataset, DeviceCachedLoader, SyntheticDiscDataset,  # noqa: E402
                       pack_samples)
-from .evaluate import (boundary_counts, compare_models_statistically, compute_aji_batch,  # noqa: E402
-                       compute_boundary_f1, compute_boundary_f1_batch, compute_hausdorff_distance,
+from .evaluate import (ProbabilityTable, best_threshold_batch, boundary_counts,  # noqa: E402
+                       compare_models_statistically, compute_aji_batch, compute_auroc_batch,
+                       compute_average_precision_batch, compute_boundary_f1, compute_boundary_f1_batch,
+                       compute_brier_batch, compute_ece_batch, compute_hausdorff_distance,
                        compute_hausdorff_distance_batch, compute_iou, compute_iou_batch, compute_object_f1_batch,
                        compute_statistics, evaluate_model, evaluate_on_test_set, extract_boundaries_device,
-                       format_metric_report, label_components, object_counts)
+                       format_metric_report, label_components, object_counts, probability_table,
+                       threshold_sweep_counts)
 from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
@@ -35,4 +38,6 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            # build additions
            "SyntheticDiscDataset", "count_parameters", "train_epoch", "AdamW", "boundary_counts",
            "extract_boundaries_device", "compute_hausdorff_distance_batch", "DeviceCachedLoader", "pack_samples",
-           "AffineAugment", "object_counts", "label_components", "compute_object_f1_batch", "compute_aji_batch"]
+           "AffineAugment", "object_counts", "label_components", "compute_object_f1_batch", "compute_aji_batch",
+           "probability_table", "threshold_sweep_counts", "compute_auroc_batch", "compute_average_precision_batch",
+           "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable"]

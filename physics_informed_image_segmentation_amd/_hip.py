@@ -20,6 +20,7 @@ PIS_RELU, PIS_SCALE, PIS_MASK, PIS_ACCUMULATE, PIS_WINO_PREPARED, PIS_W_UNFLIPPE
 PIS_FILTER_READY = 64
 PIS_LOSS_ALL_TERMS, PIS_LOSS_CHAIN_SIGMOID, PIS_LOSS_NO_REACTION = 1, 2, 4
 PIS_TUNE_LAST_WGRAD_MAIN = 42  # include/pis_capi.h: host schedule knob (unet.py)
+PIS_TUNE_PROB_VARIANT = 52  # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
 LOSS_NTERMS = 8
@@ -107,6 +108,8 @@ _SIGNATURES = {
     "pis_boundary_metrics": ([P, P, I, I, I, c_float, I, P, P, P, P, Z, P], c_int),
     "pis_objects_ws": ([I, I, I], c_size_t),
     "pis_object_metrics": ([P, P, I, I, I, c_float, I, I, P, P, P, P, Z, P], c_int),
+    "pis_probability_ws": ([I, I, I], c_size_t),
+    "pis_probability_table": ([P, P, I, I, I, P, P, P, Z, P], c_int),
     "pis_cache_batch": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
     "pis_cache_batch_affine": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
 }

@@ -34,6 +34,12 @@
   counters per sample. ``object_counts`` / ``label_components`` run on the GPU for CUDA tensors
   (csrc/components.hip, pis_object_metrics) and by scipy.ndimage.label + numpy otherwise; the two
   agree with == (tests/test_objects_gpu.py). ``evaluate_model(object_metrics=True)`` adds them.
+* Probability-level metrics (no reference counterpart): Dice / IoU at every threshold j / 1024 with
+  the best threshold, AUROC, average precision, ECE and the Brier score, all from one exact integer
+  table per sample (``probability_table``: csrc/probability.hip, pis_probability_table for CUDA
+  tensors, numpy otherwise; == in tests/test_probability_gpu.py). They are the metrics of the
+  probabilities rounded up to 16 fractional bits, with thresholds and rank ties on a 1 / 1024 grid.
+  ``evaluate_model(probability_metrics=True)`` adds them; ``ProbabilityTable`` pools a loader.
 """
 from __future__ import annotations
 
@@ -407,21 +413,304 @@ def compute_aji_batch(predictions: torch.Tensor, targets: torch.Tensor, threshol
     return _aji_from_counts(object_counts(predictions, targets, threshold, connectivity, min_area, backend))
 
 
+# ----------------------------------------------------------------------------
+# Probability-level metrics: threshold sweep, AUROC, average precision, ECE, Brier
+# (csrc/probability.hip)
+# ----------------------------------------------------------------------------
+# Definitions (include/pis_capi.h). Everything derives from one integer table per
+# sample. Per pixel, with every float step exact in fp32:
+#   x = p * 65536;  q = clamp(ceil(x), 0, 65536) (NaN: 0, counted in n_nan);  bin = (q + 63) >> 6
+#   cls = t > 0.5 (the target test of the Dice / IoU counters; a NaN target is class 0)
+#   table[b][cls][bin] = (count, sum of q);  extra[b] = (sum q^2 class 0, sum q^2 class 1, n_nan, 0)
+# so that p > j / 1024 holds exactly when bin > j (j = 0..1023; strict, NaN is background). The
+# scores below are torch integer arithmetic on that table up to one final float64 division, the
+# same code for the device path (pis_probability_table) and the host path (numpy): the two tables
+# agree with ==. What is quantised: all scores are those of the probabilities rounded UP to 16
+# fractional bits; thresholds lie on the 10-bit grid j / 1024; AUROC and average precision treat
+# the pixels of one 1 / 1024 bin as tied.
+
+PROB_BINS, PROB_QBITS = 1024, 16
+PROB_ONE = 1 << PROB_QBITS
+PROB_BLOCK_PIXELS = 8192  # csrc/probability.hip PB_PIX: the pixels one block of the histogram kernel counts
+PROB_NEG, PROB_POS = 0, 1
+
+
+def _check_calibration_bins(n_bins: int) -> int:
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 1 <= n_bins <= PROB_BINS \
+            or n_bins & (n_bins - 1):
+        raise ValueError(f"n_bins must be a power of two in 1..{PROB_BINS}, got {n_bins!r}")
+    return int(n_bins)
+
+
+def _probability_host(predictions: torch.Tensor, targets: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+    """(table (B, 2, 1025, 2) int64, extra (B, 4) int64) by numpy, from the definitions above."""
+    p, t = _bhw(predictions).cpu().numpy(), _bhw(targets).cpu().numpy()
+    if p.shape != t.shape:
+        raise ValueError(f"predictions {p.shape} and targets {t.shape} differ")
+    B = p.shape[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = p * np.float32(PROB_ONE)
+        # p > 0 is False for NaN, -Inf, negatives and both zeros: q = 0. A positive p whose x
+        # underflows still has ceil(x) = 1.
+        q = np.where(p > 0, np.clip(np.ceil(x), 1, PROB_ONE), 0).astype(np.int64)
+        cls = (t > np.float32(0.5)).astype(np.int64)
+    key = (cls * (PROB_BINS + 1) + ((q + 63) >> 6)).reshape(B, -1)
+    q, cls, nan = q.reshape(B, -1), cls.reshape(B, -1), np.isnan(p).reshape(B, -1)
+    table = np.zeros((B, 2 * (PROB_BINS + 1), 2), np.int64)
+    extra = np.zeros((B, 4), np.int64)
+    for b in range(B):
+        table[b, :, 0] = np.bincount(key[b], minlength=2 * (PROB_BINS + 1))
+        # float64 weights: every partial sum is an integer below 2^40, exact
+        table[b, :, 1] = np.bincount(key[b], weights=q[b].astype(np.float64), minlength=2 * (PROB_BINS + 1))
+        q2 = q[b] * q[b]
+        extra[b, 0], extra[b, 1], extra[b, 2] = q2[cls[b] == 0].sum(), q2[cls[b] == 1].sum(), nan[b].sum()
+    return table.reshape(B, 2, PROB_BINS + 1, 2), extra
+
+
+def _probability_device(predictions: torch.Tensor, targets: torch.Tensor, ws: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pis_probability_table call (two launches) on the current stream: (table, extra). ``ws``:
+    a uint8 CUDA tensor of at least pis_probability_ws bytes to use as the workspace (its contents
+    do not matter); allocated from the caching allocator when None."""
+    p, t = _bhw(predictions), _bhw(targets)
+    _hip.require_cuda(p, "probability_table")
+    _hip.require_cuda(t, "probability_table")
+    if p.shape != t.shape or p.device != t.device:
+        raise ValueError(f"predictions {tuple(p.shape)} on {p.device} and targets {tuple(t.shape)} on {t.device} differ")
+    B, H, W = p.shape
+    with torch.cuda.device(p.device):
+        nbytes = _hip.lib().pis_probability_ws(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"probability_table: unsupported shape B={B} H={H} W={W} (B >= 1, 1 <= H, W <= 4096)")
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+        table = torch.empty((B, 2, PROB_BINS + 1, 2), dtype=torch.int64, device=p.device)
+        extra = torch.empty((B, 4), dtype=torch.int64, device=p.device)
+        _hip.call("pis_probability_table", _hip.ptr(p), _hip.ptr(t), B, H, W, _hip.ptr(table), _hip.ptr(extra),
+                  _hip.ptr(ws), ws.numel(), _hip.stream_handle(p.device))
+    return table, extra
+
+
+def probability_table(predictions: torch.Tensor, targets: torch.Tensor, backend: str = "auto"
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(table (B, 2, 1025, 2) int64, extra (B, 4) int64) of a (B, H, W) or (B, 1, H, W) batch:
+    ``table[b, cls, bin] = (count, sum of q)`` and ``extra[b] = (sum q^2 over class 0, over class 1,
+    n_nan, 0)`` with q the probability rounded UP to 16 fractional bits, bin = ceil(p * 1024) clamped to
+    0..1024 and cls = t > 0.5. CUDA tensors: on their device, one pis_probability_table call, no host
+    synchronisation. CPU tensors (and ``backend="host"``): numpy, CPU tensors; the two agree exactly."""
+    if _use_device(backend, predictions, targets):
+        return _probability_device(predictions, targets)
+    table, extra = _probability_host(predictions, targets)
+    return torch.from_numpy(table), torch.from_numpy(extra)
+
+
+def _as_table(a, b, backend: str, need_extra: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(predictions, targets) -> their table; a table, or a (table, extra) pair, passes through."""
+    if b is None:
+        table, extra = a if isinstance(a, (tuple, list)) else (a, None)
+    else:
+        table, extra = probability_table(a, b, backend)
+    if table.dtype != torch.int64 or table.dim() != 4 or tuple(table.shape[1:]) != (2, PROB_BINS + 1, 2):
+        raise ValueError(f"need an int64 table of shape (B, 2, {PROB_BINS + 1}, 2), got {table.dtype} "
+                         f"{tuple(table.shape)} (or pass predictions and targets)")
+    if need_extra and (extra is None or extra.dtype != torch.int64 or tuple(extra.shape) != (table.shape[0], 4)):
+        raise ValueError("the Brier score needs (table, extra) as returned by probability_table")
+    return table, extra
+
+
+def _nan_where(cond: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    return torch.where(cond, torch.full_like(x, float("nan")), x)
+
+
+def _suffix_sum(x: torch.Tensor) -> torch.Tensor:
+    """out[..., i] = sum over k >= i of x[..., k]."""
+    return x.flip(-1).cumsum(-1).flip(-1)
+
+
+def threshold_sweep_counts(table: torch.Tensor) -> torch.Tensor:
+    """(B, 1024, 3) int64 ``(I_hat, P_hat, T)`` at the thresholds j / 1024, j = 0..1023, from a table:
+    the counters ``sample_counts(p, t, j / 1024)`` returns (row 512: threshold 0.5). Exact."""
+    table, _ = _as_table(table, None, "auto")
+    pos, neg = table[:, PROB_POS, :, 0], table[:, PROB_NEG, :, 0]
+    i_hat = _suffix_sum(pos)[:, 1:]              # bins above j
+    p_hat = _suffix_sum(pos + neg)[:, 1:]
+    return torch.stack([i_hat, p_hat, pos.sum(-1, keepdim=True).expand_as(i_hat)], dim=-1)
+
+
+def _sweep_scores(counts: torch.Tensor, smooth: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Dice, IoU) per threshold in float64 by the formulas of the fused counters."""
+    i_hat, p_hat, t = counts.to(torch.float64).unbind(-1)
+    return (2.0 * i_hat + smooth) / (p_hat + t + smooth), (i_hat + smooth) / (p_hat + t - i_hat + smooth)
+
+
+def best_threshold_batch(predictions, targets=None, backend: str = "auto", smooth: float = 1e-6
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per sample the first threshold j / 1024 that maximises the Dice score, and that score: two
+    float64 tensors on the table's device. Takes (predictions, targets) or a table."""
+    table, _ = _as_table(predictions, targets, backend)
+    dice, _ = _sweep_scores(threshold_sweep_counts(table), smooth)
+    j = torch.argmax(dice, dim=1)  # the first maximum
+    return j.to(torch.float64) / PROB_BINS, dice.gather(1, j[:, None])[:, 0]
+
+
+def compute_auroc_batch(predictions, targets=None, backend: str = "auto") -> torch.Tensor:
+    """Per-sample area under the ROC curve of the 1025-bin ranking, float64 on the table's device:
+    sum_i pos_i (2 below_i + neg_i) / (2 P Nn), the pixels of one 1 / 1024 bin counted as ties (half).
+    NaN for a sample without positives or without negatives. Takes (predictions, targets) or a table."""
+    table, _ = _as_table(predictions, targets, backend)
+    pos, neg = table[:, PROB_POS, :, 0], table[:, PROB_NEG, :, 0]
+    below = neg.cumsum(-1) - neg
+    num = (pos * (2 * below + neg)).sum(-1)        # below 2^50
+    den = 2 * pos.sum(-1) * neg.sum(-1)
+    return _nan_where(den == 0, num.to(torch.float64) / den.to(torch.float64))
+
+
+def compute_average_precision_batch(predictions, targets=None, backend: str = "auto") -> torch.Tensor:
+    """Per-sample average precision in the step form over the bins from 1024 down to 0:
+    sum_i (pos_i / P) (TP_i / PP_i) with TP_i, PP_i the positives / all pixels in bins >= i (terms
+    with PP_i = 0 are empty). float64; NaN for a sample without positives."""
+    table, _ = _as_table(predictions, targets, backend)
+    pos, neg = table[:, PROB_POS, :, 0], table[:, PROB_NEG, :, 0]
+    tp, pp = _suffix_sum(pos), _suffix_sum(pos + neg)
+    p_all = pos.sum(-1, keepdim=True)
+    den = p_all * pp
+    terms = (pos * tp).to(torch.float64) / den.clamp_min(1).to(torch.float64)   # pos_i = 0 where den = 0
+    return _nan_where(p_all[:, 0] == 0, terms.sum(-1))
+
+
+def _coarse_bins(table: torch.Tensor, n_bins: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(count, positives, sum of q) per coarse bin, (B, n_bins) int64 each: coarse bin m holds the
+    fine bins i with (i - 1) // (1024 / n_bins) == m, and fine bin 0 (q = 0) joins m = 0."""
+    both = table[:, PROB_NEG] + table[:, PROB_POS]                      # (B, 1025, 2)
+    B = table.shape[0]
+
+    def fold(x):
+        y = x[:, 1:].reshape(B, n_bins, PROB_BINS // n_bins).sum(-1)
+        y[:, 0] += x[:, 0]
+        return y
+    return fold(both[..., 0]), fold(table[:, PROB_POS, :, 0]), fold(both[..., 1])
+
+
+def compute_ece_batch(predictions, targets=None, n_bins: int = 16, backend: str = "auto") -> torch.Tensor:
+    """Per-sample expected calibration error with ``n_bins`` equal-width confidence bins (a power of
+    two up to 1024): sum_m |SQ_m - 65536 pos_m| / (65536 N), i.e. sum_m (n_m / N) |mean confidence -
+    positive fraction| of the probabilities rounded up to 16 bits. float64."""
+    n_bins = _check_calibration_bins(n_bins)
+    table, _ = _as_table(predictions, targets, backend)
+    count, pos, sq = _coarse_bins(table, n_bins)
+    num = (sq - PROB_ONE * pos).abs().sum(-1)
+    return num.to(torch.float64) / (PROB_ONE * count.sum(-1)).to(torch.float64)
+
+
+def compute_brier_batch(predictions, targets=None, backend: str = "auto") -> torch.Tensor:
+    """Per-sample Brier score mean((q / 65536 - cls)^2) from the integer sums:
+    (S2_neg + S2_pos - 2 * 65536 SQ_pos + 2^32 P) / (2^32 N). float64. Takes (predictions, targets)
+    or the pair (table, extra)."""
+    table, extra = _as_table(predictions, targets, backend, need_extra=True)
+    pos = table[:, PROB_POS]
+    n = table[..., 0].sum((1, 2))
+    num = extra[:, 0] + extra[:, 1] - 2 * PROB_ONE * pos[..., 1].sum(-1) + (PROB_ONE * PROB_ONE) * pos[..., 0].sum(-1)
+    return num.to(torch.float64) / ((PROB_ONE * PROB_ONE) * n).to(torch.float64)
+
+
+class ProbabilityTable:
+    """The pooled table of a whole loader: ``update`` adds every sample of a batch's table (on the
+    table's device; integers, so pooling is exact and does not depend on the order), and the pooled
+    curves and scores come from the sums by the same arithmetic as the per-sample ones."""
+
+    def __init__(self):
+        self.table: Optional[torch.Tensor] = None   # (2, 1025, 2) int64
+        self.extra: Optional[torch.Tensor] = None   # (4,) int64
+
+    def update(self, table: torch.Tensor, extra: torch.Tensor) -> "ProbabilityTable":
+        table, extra = _as_table((table, extra), None, "auto", need_extra=True)
+        if self.table is None:
+            self.table, self.extra = table.sum(0), extra.sum(0)
+        else:
+            self.table += table.sum(0).to(self.table.device)
+            self.extra += extra.sum(0).to(self.extra.device)
+        return self
+
+    def _batch(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.table is None:
+            raise ValueError("ProbabilityTable: no batch has been added yet")
+        return self.table[None], self.extra[None]
+
+    @property
+    def total_count(self) -> int:
+        return 0 if self.table is None else int(self.table[..., 0].sum())
+
+    def sweep(self) -> Dict[str, torch.Tensor]:
+        """Pooled per-threshold curves, 1024 rows: ``threshold`` j / 1024, ``tp``, ``fp``, ``fn``
+        (int64), ``precision`` (NaN where nothing is predicted), ``recall`` (NaN without positives),
+        ``dice`` and ``iou`` (the smoothed formulas of the per-image scores), float64."""
+        c = threshold_sweep_counts(self._batch()[0])[0]
+        tp, fp, fn = c[:, 0], c[:, 1] - c[:, 0], c[:, 2] - c[:, 0]
+        dice, iou = _sweep_scores(c)
+        f = torch.float64
+        return {"threshold": torch.arange(PROB_BINS, dtype=f, device=c.device) / PROB_BINS, "tp": tp, "fp": fp,
+                "fn": fn, "precision": _nan_where(c[:, 1] == 0, tp.to(f) / c[:, 1].to(f)),
+                "recall": _nan_where(c[:, 2] == 0, tp.to(f) / c[:, 2].to(f)), "dice": dice, "iou": iou}
+
+    def best_threshold(self) -> Tuple[float, float]:
+        """(threshold, Dice): the first threshold j / 1024 that maximises the pooled Dice score."""
+        thr, dice = best_threshold_batch(self._batch()[0])
+        return float(thr[0]), float(dice[0])
+
+    def reliability(self, n_bins: int = 16) -> Dict[str, torch.Tensor]:
+        """Per confidence bin (``n_bins`` equal-width bins, a power of two up to 1024): ``count``
+        (int64), ``mean_confidence`` and ``positive_fraction`` (float64, NaN for an empty bin)."""
+        n_bins = _check_calibration_bins(n_bins)
+        count, pos, sq = (x[0] for x in _coarse_bins(self._batch()[0], n_bins))
+        f = torch.float64
+        return {"count": count, "mean_confidence": _nan_where(count == 0, sq.to(f) / (PROB_ONE * count).to(f)),
+                "positive_fraction": _nan_where(count == 0, pos.to(f) / count.to(f))}
+
+    def auroc(self) -> float:
+        return float(compute_auroc_batch(self._batch()[0])[0])
+
+    def average_precision(self) -> float:
+        return float(compute_average_precision_batch(self._batch()[0])[0])
+
+    def ece(self, n_bins: int = 16) -> float:
+        return float(compute_ece_batch(self._batch()[0], n_bins=n_bins)[0])
+
+    def brier(self) -> float:
+        return float(compute_brier_batch(self._batch())[0])
+
+
+_probability_table_of_batch = probability_table  # evaluate_model has a parameter of that name
+# the per-image arrays evaluate_model(probability_metrics=True) adds, in this order
+PROBABILITY_METRIC_KEYS = ("auroc_scores", "average_precision_scores", "ece_scores", "brier_scores",
+                           "best_threshold_dice_scores", "best_thresholds")
+
+
 @torch.no_grad()
 def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_metrics: bool = True,
                    boundary_backend: str = "auto", object_metrics: bool = False, connectivity: int = 8,
-                   min_object_area: int = 0, object_backend: str = "auto") -> Dict[str, np.ndarray]:
+                   min_object_area: int = 0, object_backend: str = "auto", probability_metrics: bool = False,
+                   calibration_bins: int = 16, probability_backend: str = "auto",
+                   probability_table: Optional[ProbabilityTable] = None) -> Dict[str, np.ndarray]:
     """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
     (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
     ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
     "host" or "device", as ``compute_boundary_f1_batch``). ``object_metrics=True`` adds
     ``object_f1_scores`` (IoU > 0.5), ``aji_scores`` and ``object_count_errors`` (n_p - n_t) from
-    one ``object_counts`` call and one device->host copy per batch."""
+    one ``object_counts`` call and one device->host copy per batch. ``probability_metrics=True``
+    adds ``auroc_scores``, ``average_precision_scores``, ``ece_scores`` (``calibration_bins`` bins),
+    ``brier_scores``, ``best_threshold_dice_scores`` and ``best_thresholds`` from one
+    ``probability_table`` call and one device->host copy per batch; a ``ProbabilityTable`` passed as
+    ``probability_table`` is updated with every batch (the pooled curves of the loader)."""
+    if probability_metrics:  # refused before any GPU work
+        calibration_bins = _check_calibration_bins(calibration_bins)
+        if probability_backend not in ("auto", "host", "device"):
+            raise ValueError(f"backend must be 'auto', 'host' or 'device', got {probability_backend!r}")
     model.eval()
     if object_metrics:
         _check_objects(connectivity, min_object_area)
     dice, iou, bf1, hd = [], [], [], []
     of1, aji, cerr = [], [], []
+    prob = [[] for _ in range(6)]
     for images, masks in dataloader:
         images, masks = images.to(device, non_blocking=True), masks.to(device, non_blocking=True)
         outputs = model(images)
@@ -449,6 +738,16 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
             of1.extend(three[0].tolist())
             aji.extend(three[1].tolist())
             cerr.extend(three[2].tolist())
+        if probability_metrics:
+            table, extra = _probability_table_of_batch(outputs, masks, probability_backend)
+            if probability_table is not None:
+                probability_table.update(table, extra)
+            thr, thr_dice = best_threshold_batch(table)
+            six = torch.stack([compute_auroc_batch(table), compute_average_precision_batch(table),
+                               compute_ece_batch(table, n_bins=calibration_bins), compute_brier_batch((table, extra)),
+                               thr_dice, thr]).cpu().numpy()
+            for acc, row in zip(prob, six):
+                acc.extend(row.tolist())
     out = {"dice_scores": np.array(dice), "iou_scores": np.array(iou)}
     if boundary_metrics:
         out["boundary_f1_scores"] = np.array(bf1)
@@ -457,6 +756,9 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
         out["object_f1_scores"] = np.array(of1)
         out["aji_scores"] = np.array(aji)
         out["object_count_errors"] = np.array(cerr)
+    if probability_metrics:
+        for key, acc in zip(PROBABILITY_METRIC_KEYS, prob):
+            out[key] = np.array(acc, dtype=np.float64)
     return out
 
 
@@ -514,11 +816,17 @@ def format_metric_report(metrics: Dict[str, np.ndarray], model_name: str = "Mode
 
 def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8, threshold: float = 0.5,
                          model_name: str = "Model", device_cache: bool = False, object_metrics: bool = False,
-                         connectivity: int = 8, min_object_area: int = 0) -> Dict[str, np.ndarray]:
+                         connectivity: int = 8, min_object_area: int = 0, probability_metrics: bool = False,
+                         calibration_bins: int = 16,
+                         probability_table: Optional[ProbabilityTable] = None) -> Dict[str, np.ndarray]:
     """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
     ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
     (``dataset.DeviceCachedLoader``) instead of ``DataLoader`` workers; a set that does not fit
-    falls back to them. ``object_metrics=True`` adds the object-level arrays of ``evaluate_model``."""
+    falls back to them. ``object_metrics=True`` adds the object-level arrays of ``evaluate_model``,
+    ``probability_metrics=True`` its probability-level arrays (ECE over ``calibration_bins`` bins;
+    a ``ProbabilityTable`` passed as ``probability_table`` receives the pooled table of the set)."""
+    if probability_metrics:
+        _check_calibration_bins(calibration_bins)
     from torch.utils.data import DataLoader
 
     from .dataset import CellSegmentationDataset, DeviceCachedLoader
@@ -538,7 +846,9 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
                             pin_memory=torch.cuda.is_available())
     print(f"Test samples: {len(ds)}")
     metrics = evaluate_model(model, loader, device, threshold=threshold, object_metrics=object_metrics,
-                             connectivity=connectivity, min_object_area=min_object_area)
+                             connectivity=connectivity, min_object_area=min_object_area,
+                             probability_metrics=probability_metrics, calibration_bins=calibration_bins,
+                             probability_table=probability_table)
     print(format_metric_report(metrics, model_name=model_name))
     return metrics
 
@@ -548,4 +858,6 @@ __all__ = ["compute_iou", "compute_iou_batch", "extract_boundaries", "compute_bo
            "extract_boundaries_device", "compute_hausdorff_distance_batch", "evaluate_model",
            "compute_dice_score_batch", "compute_statistics", "compare_models_statistically",
            "format_metric_report", "evaluate_on_test_set", "object_counts", "label_components",
-           "compute_object_f1_batch", "compute_aji_batch"]
+           "compute_object_f1_batch", "compute_aji_batch", "probability_table", "threshold_sweep_counts",
+           "compute_auroc_batch", "compute_average_precision_batch", "compute_ece_batch", "compute_brier_batch",
+           "best_threshold_batch", "ProbabilityTable"]

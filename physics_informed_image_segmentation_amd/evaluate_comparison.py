@@ -19,15 +19,19 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from .evaluate import compare_models_statistically, compute_statistics, evaluate_on_test_set, format_metric_report
+from .evaluate import (PROBABILITY_METRIC_KEYS, ProbabilityTable, compare_models_statistically, compute_statistics,
+                       evaluate_on_test_set, format_metric_report)
 from .unet import UNet
 
 METRIC_KEYS = ("dice_scores", "iou_scores", "boundary_f1_scores", "hausdorff_distances")
 # appended only when the object-level metrics are switched on (evaluate.py: evaluate_model)
 OBJECT_METRIC_KEYS = ("object_f1_scores", "aji_scores", "object_count_errors")
+# PROBABILITY_METRIC_KEYS (evaluate.py) likewise, only with the probability-level metrics switched on
 _COLUMNS = {"dice_scores": "dice", "iou_scores": "iou", "boundary_f1_scores": "boundary_f1",
             "hausdorff_distances": "hausdorff", "object_f1_scores": "object_f1", "aji_scores": "aji",
-            "object_count_errors": "object_count_error"}
+            "object_count_errors": "object_count_error", "auroc_scores": "auroc",
+            "average_precision_scores": "average_precision", "ece_scores": "ece", "brier_scores": "brier",
+            "best_threshold_dice_scores": "best_threshold_dice", "best_thresholds": "best_threshold"}
 _DEFAULT_OUT = Path(__file__).resolve().parent.parent / "output"
 
 
@@ -79,26 +83,35 @@ def _print_comparison(results: Dict[str, Dict[str, float]]):
 def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_dir: Path, test_json: Path,
                          device: torch.device, batch_size: int = 8, threshold: float = 0.5,
                          output_dir: Optional[Path] = None, device_cache: bool = False,
-                         object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0) -> Dict:
+                         object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0,
+                         probability_metrics: bool = False, calibration_bins: int = 16) -> Dict:
+    """``probability_metrics=True`` adds the six probability-level columns and rows and writes, per
+    model, threshold_sweep_<model>_<ts>.csv (the pooled curves, 1024 rows) and
+    reliability_<model>_<ts>.csv (``calibration_bins`` rows); the pooled best thresholds go into
+    the comparison JSON under "pooled_best_threshold"."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
     obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
+    pooled = {"baseline": ProbabilityTable(), "pde": ProbabilityTable()} if probability_metrics else {}
+    prob = {tag: dict(probability_metrics=True, calibration_bins=calibration_bins, probability_table=tab)
+            for tag, tab in pooled.items()}
     print("=" * 70 + "\nMODEL EVALUATION AND STATISTICAL COMPARISON\n" + "=" * 70)
     print("\nLoading models...")
     base = evaluate_on_test_set(load_model(baseline_model_path, device), test_dir, test_json, device,
                                 batch_size=batch_size, threshold=threshold, model_name="Baseline (Unconstrained)",
-                                device_cache=device_cache, **obj)
+                                device_cache=device_cache, **obj, **prob.get("baseline", {}))
     pde = evaluate_on_test_set(load_model(pde_model_path, device), test_dir, test_json, device,
                                batch_size=batch_size, threshold=threshold, model_name="PDE-Constrained",
-                               device_cache=device_cache, **obj)
+                               device_cache=device_cache, **obj, **prob.get("pde", {}))
     print("\n" + "=" * 70 + "\nSTATISTICAL COMPARISON\n" + "=" * 70)
     cmp = compare_models_statistically(base, pde, alpha=0.05)
     _print_comparison(cmp)
 
     ts = datetime.now().strftime("%Y%m%d_%H%M%S")
     per_image = {"image_id": range(len(base["dice_scores"]))}
-    for key in METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ()):
+    for key in (METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
+                + (PROBABILITY_METRIC_KEYS if probability_metrics else ())):
         col = _COLUMNS[key]
         per_image[f"baseline_{col}"] = base[key]
         per_image[f"pde_{col}"] = pde[key]
@@ -117,22 +130,44 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
     pd.DataFrame(summary).T.to_csv(summary_csv)
     print(f"Summary statistics saved to: {summary_csv}")
     comparison_json = out_dir / f"statistical_comparison_{ts}.json"
+    payload, files = dict(cmp), {}
+    if probability_metrics:
+        payload["pooled_best_threshold"] = {}
+        for tag, tab in pooled.items():
+            thr, dice = tab.best_threshold()
+            payload["pooled_best_threshold"][tag] = {"threshold": thr, "dice": dice}
+            print(f"Pooled best threshold ({tag}): {thr:.4f} (Dice {dice:.4f})")
+            sweep_csv = out_dir / f"threshold_sweep_{tag}_{ts}.csv"
+            pd.DataFrame({k: v.cpu().numpy() for k, v in tab.sweep().items()}).to_csv(sweep_csv, index=False)
+            reliability_csv = out_dir / f"reliability_{tag}_{ts}.csv"
+            rel = {"bin": range(calibration_bins)}
+            rel.update({k: v.cpu().numpy() for k, v in tab.reliability(calibration_bins).items()})
+            pd.DataFrame(rel).to_csv(reliability_csv, index=False)
+            print(f"Threshold sweep and reliability table ({tag}) saved to: {sweep_csv}, {reliability_csv}")
+            files[f"threshold_sweep_{tag}_csv"], files[f"reliability_{tag}_csv"] = sweep_csv, reliability_csv
+        files["pooled_best_threshold"] = payload["pooled_best_threshold"]
     with open(comparison_json, "w") as f:
-        json.dump(make_json_serializable(cmp), f, indent=2)
+        json.dump(make_json_serializable(payload), f, indent=2)
     print(f"Statistical comparison saved to: {comparison_json}")
     return {"baseline_metrics": base, "pde_metrics": pde, "comparison_results": cmp, "results_csv": results_csv,
-            "summary_csv": summary_csv, "comparison_json": comparison_json}
+            "summary_csv": summary_csv, "comparison_json": comparison_json, **files}
 
 
 def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: List[Path], test_dir: Path,
                              test_json: Path, device: torch.device, batch_size: int = 8, threshold: float = 0.5,
                              output_dir: Optional[Path] = None, device_cache: bool = False,
-                             object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0) -> Dict:
+                             object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0,
+                             probability_metrics: bool = False, calibration_bins: int = 16) -> Dict:
+    """``probability_metrics=True`` adds the six per-image probability-level arrays to the pooled
+    statistics (the per-model sweep and reliability files belong to ``evaluate_and_compare``)."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
     obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
-    metric_keys = METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
+    if probability_metrics:
+        obj.update(probability_metrics=True, calibration_bins=calibration_bins)
+    metric_keys = (METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
+                   + (PROBABILITY_METRIC_KEYS if probability_metrics else ()))
     print("=" * 70 + "\nREPEATED EXPERIMENTS EVALUATION\n" + "=" * 70)
     print(f"Number of runs: {len(baseline_model_paths)}")
     pooled = {"baseline": {k: [] for k in metric_keys}, "pde": {k: [] for k in metric_keys}}
@@ -168,5 +203,5 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
     return {"baseline_metrics": base, "pde_metrics": pde, "comparison_results": cmp, "aggregated_csv": aggregated_csv}
 
 
-__all__ = ["METRIC_KEYS", "OBJECT_METRIC_KEYS", "make_json_serializable", "load_model", "evaluate_and_compare",
-           "run_repeated_evaluations"]
+__all__ = ["METRIC_KEYS", "OBJECT_METRIC_KEYS", "PROBABILITY_METRIC_KEYS", "make_json_serializable", "load_model",
+           "evaluate_and_compare", "run_repeated_evaluations"]
