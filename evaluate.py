@@ -55,6 +55,9 @@ def parse_args(argv=None):
     ap.add_argument("--calibration-bins", type=_calibration_bins, default=16, metavar="N",
                     help="confidence bins of the ECE and the reliability table for --probability-metrics: a power "
                          "of two up to 1024 (default: 16)")
+    ap.add_argument("--tta", choices=["flip", "d4"], default=None,
+                    help="evaluate both models under test-time augmentation: average the predictions over the 4 "
+                         "flips or all 8 symmetries of the grid (tiled prediction on the GPU; default: off)")
     return ap.parse_args(argv)
 
 
@@ -75,6 +78,8 @@ def main(argv=None):
         common.update(object_metrics=True, connectivity=args.connectivity, min_object_area=args.min_object_area)
     if args.probability_metrics:
         common.update(probability_metrics=True, calibration_bins=args.calibration_bins)
+    if args.tta:
+        common["tta"] = args.tta
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

@@ -717,6 +717,59 @@ int pis_cache_batch_affine(const void* img, int img_fmt, size_t img_stride, cons
                            size_t mask_stride, const float* norm, const int64_t* idx, const void* params,
                            int64_t N, float* img_out, float* mask_out, int B, int H, int W, pis_stream_t stream);
 
+/* ---- whole-image inference: overlapping tiles under test-time symmetries, gathered before the forwards
+ * and blended after them (no reference counterpart; predict.py:Predictor) ----
+ * The tiling is a pure function of the by-value arguments; predict.py:tile_plan / gather_tiles_np /
+ * blend_tiles_np restate it in float32 numpy and agree bit for bit.
+ * Tile origins: along an axis of length n with tile t and overlap o the stride is t - o,
+ *   K(n, t, o)  = 1 if n <= t, else ceil((n - o) / (t - o))
+ *   origin(k)   = min(k (t - o), max(n - t, 0))     the last tile is pulled back to end at the image edge;
+ *                                                   a single tile on an axis shorter than t starts at 0 and
+ *                                                   its excess is reflection
+ * Ky = K(H, th, ov), Kx = K(W, tw, ov). Symmetries: sym_mask is a non-empty 8-bit set of the codes of
+ * pis_cache_batch (bit 0 flips W, bit 1 flips H, then bit 2 transposes); bit q set means code q is used, in
+ * ascending order, Ns = popcount(sym_mask); a code >= 4 needs th == tw. Jobs are numbered
+ *   j = ((s Ky + ky) Kx + kx) Ns + qi               for source s of S, J = S Ky Kx Ns jobs in all.
+ * reflect(i, n) is the one of pis_cache_batch_affine: it wraps as often as needed, so a 5 x 7 image under a
+ * 16 x 16 tile is defined.
+ *
+ * pis_tile_count: Ky and Kx of one image, on the host (no GPU call).
+ *
+ * pis_tile_gather: one launch writes out (n_jobs, 1, th, tw) fp32 contiguous for the jobs
+ * [first_job, first_job + n_jobs). The S sources are H x W images in one of the cache's two image formats,
+ * source s at src + s * src_stride (bytes, a multiple of 16, at least one image long; base 16-byte aligned):
+ * PIS_CACHE_IMG_U8 with norm[s] = (lo, den), pixel = (float(v) - lo) / den correctly rounded, or
+ * PIS_CACHE_IMG_F32, copied. With (y0, x0) = (origin(ky), origin(kx)) and q the job's code,
+ *   T[ly][lx] = src[s][reflect(y0 + ly, H)][reflect(x0 + lx, W)]        0 <= ly < th, 0 <= lx < tw
+ *   out[j - first_job] = t = T; if (q & 1) t = flip_W(t); if (q & 2) t = flip_H(t); if (q & 4) t = transpose(t).
+ *
+ * pis_tile_blend: one launch reads u (J, 1, th, tw) fp32 — one value per gathered element, for ALL J jobs —
+ * and writes prob (S, H, W) fp32 and, if mask is not NULL, mask (S, H, W) uint8 in {0, 1}. In gather form,
+ * one result per output pixel, no atomics. For pixel (s, y, x), every tile that covers it is visited in the
+ * order ky ascending, kx ascending, qi ascending; with ly = y - origin(ky), lx = x - origin(kx):
+ *   v    = the element of u[j] that the job's symmetry sent T[ly][lx] to (the inverse of the gather)
+ *   w    = w1(ly, th, ov) * w1(lx, tw, ov), an integer: w1(l, t, o) = min(l + 1, t - l, o) for o >= 1, 1 for
+ *          o == 0 (a ramp over the overlap, in the image frame: the Ns symmetries of one tile share it)
+ *   acc  = acc + float(w) * v      the multiply and the add each correctly rounded on its own (no fused
+ *                                  multiply-add), acc starting at 0.0f
+ *   wsum = wsum + w                an integer
+ *   prob = acc / float(wsum)       correctly rounded
+ *   mask = prob > thr              strict, the comparison of the loss kernel's counters; NaN gives 0
+ * ov <= 256 bounds w by 2^16, and at most 3 tiles per axis cover a pixel (two neighbours and the pulled-back
+ * last tile), so wsum over at most 3 * 3 * 8 covers is an exact integer in fp32.
+ *
+ * PIS_ERR_ARG (all three): th or tw no multiple of 16 in [16, 2048]; ov outside [0, min(th, tw) / 2] or
+ * above 256; H or W outside [1, 32768]; S < 1; an empty sym_mask or one above 0xFF; a code >= 4 with
+ * th != tw; a NULL pointer (mask may be NULL); gather: an unknown format, a u8 source without norm, a bad
+ * stride, src or out not 16-byte aligned, a chunk not within [0, J); blend: u or prob not 16-byte aligned,
+ * mask not 4-byte aligned. All indexing is 64-bit. No workspace, no state, no host synchronisation. */
+int pis_tile_count(int H, int W, int th, int tw, int ov, int* Ky, int* Kx);
+int pis_tile_gather(const void* src, int src_fmt, size_t src_stride, const float* norm, int S, int H, int W,
+                    int th, int tw, int ov, int sym_mask, int64_t first_job, int64_t n_jobs, float* out,
+                    pis_stream_t stream);
+int pis_tile_blend(const float* u, int S, int H, int W, int th, int tw, int ov, int sym_mask, float thr,
+                   float* prob, uint8_t* mask, pis_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

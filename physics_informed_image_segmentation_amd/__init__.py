@@ -28,6 +28,7 @@ from .train import EarlyStopping, train, train_epoch, train_stage, validate  # n
 from .unet import UNet, count_parameters  # noqa: E402
 from .evaluate_comparison import evaluate_and_compare, run_repeated_evaluations  # noqa: E402
 from .ablation import AblationConfig, run_ablation_study, run_ablation_variant  # noqa: E402
+from .predict import Predictor, blend_tiles_np, clean_mask, gather_tiles_np, tile_plan  # noqa: E402
 
 __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "PDERegularization",
            "create_pde_regularization", "compute_dice_score", "compute_dice_score_batch", "EarlyStopping",
@@ -40,4 +41,5 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "extract_boundaries_device", "compute_hausdorff_distance_batch", "DeviceCachedLoader", "pack_samples",
            "AffineAugment", "object_counts", "label_components", "compute_object_f1_batch", "compute_aji_batch",
            "probability_table", "threshold_sweep_counts", "compute_auroc_batch", "compute_average_precision_batch",
-           "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable"]
+           "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable",
+           "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np"]

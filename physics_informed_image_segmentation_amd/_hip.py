@@ -112,6 +112,9 @@ _SIGNATURES = {
     "pis_probability_table": ([P, P, I, I, I, P, P, P, Z, P], c_int),
     "pis_cache_batch": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
     "pis_cache_batch_affine": ([P, I, Z, P, I, Z, P, P, P, L, P, P, I, I, I, P], c_int),
+    "pis_tile_count": ([I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
+    "pis_tile_gather": ([P, I, Z, P, I, I, I, I, I, I, I, L, L, P, P], c_int),
+    "pis_tile_blend": ([P, I, I, I, I, I, I, I, c_float, P, P, P], c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -690,7 +690,8 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
                    boundary_backend: str = "auto", object_metrics: bool = False, connectivity: int = 8,
                    min_object_area: int = 0, object_backend: str = "auto", probability_metrics: bool = False,
                    calibration_bins: int = 16, probability_backend: str = "auto",
-                   probability_table: Optional[ProbabilityTable] = None) -> Dict[str, np.ndarray]:
+                   probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
+                   tta_tile: int = 512, tta_overlap: int = 64) -> Dict[str, np.ndarray]:
     """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
     (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
     ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
@@ -700,7 +701,16 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     adds ``auroc_scores``, ``average_precision_scores``, ``ece_scores`` (``calibration_bins`` bins),
     ``brier_scores``, ``best_threshold_dice_scores`` and ``best_thresholds`` from one
     ``probability_table`` call and one device->host copy per batch; a ``ProbabilityTable`` passed as
-    ``probability_table`` is updated with every batch (the pooled curves of the loader)."""
+    ``probability_table`` is updated with every batch (the pooled curves of the loader).
+    ``tta="flip"`` / ``"d4"``: the outputs are the test-time-augmented probabilities of a
+    ``predict.Predictor`` (tiles of at most ``tta_tile`` with ``tta_overlap`` overlap, 4 or 8
+    symmetries) instead of ``model(images)``; everything downstream is unchanged."""
+    predictor = None
+    if tta is not None:  # refused before any GPU work
+        from .predict import Predictor
+        if tta not in ("flip", "d4"):
+            raise ValueError(f"tta must be None, 'flip' or 'd4', got {tta!r}")
+        predictor = Predictor(model, tile=tta_tile, overlap=tta_overlap, tta=tta, threshold=threshold)
     if probability_metrics:  # refused before any GPU work
         calibration_bins = _check_calibration_bins(calibration_bins)
         if probability_backend not in ("auto", "host", "device"):
@@ -713,7 +723,7 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     prob = [[] for _ in range(6)]
     for images, masks in dataloader:
         images, masks = images.to(device, non_blocking=True), masks.to(device, non_blocking=True)
-        outputs = model(images)
+        outputs = model(images) if predictor is None else predictor.predict_batch(images)[0]
         _, scores = sample_counts(outputs, masks, threshold)
         s = scores.cpu().numpy()
         dice.extend(s[:, 0].tolist())
@@ -818,15 +828,18 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
                          model_name: str = "Model", device_cache: bool = False, object_metrics: bool = False,
                          connectivity: int = 8, min_object_area: int = 0, probability_metrics: bool = False,
                          calibration_bins: int = 16,
-                         probability_table: Optional[ProbabilityTable] = None) -> Dict[str, np.ndarray]:
+                         probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
+                         tta_tile: int = 512, tta_overlap: int = 64) -> Dict[str, np.ndarray]:
     """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
     ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
     (``dataset.DeviceCachedLoader``) instead of ``DataLoader`` workers; a set that does not fit
     falls back to them. ``object_metrics=True`` adds the object-level arrays of ``evaluate_model``,
     ``probability_metrics=True`` its probability-level arrays (ECE over ``calibration_bins`` bins;
-    a ``ProbabilityTable`` passed as ``probability_table`` receives the pooled table of the set)."""
+    a ``ProbabilityTable`` passed as ``probability_table`` receives the pooled table of the set).
+    ``tta``, ``tta_tile``, ``tta_overlap``: test-time augmentation, as ``evaluate_model``."""
     if probability_metrics:
         _check_calibration_bins(calibration_bins)
+    tta_kw = {} if tta is None else dict(tta=tta, tta_tile=tta_tile, tta_overlap=tta_overlap)
     from torch.utils.data import DataLoader
 
     from .dataset import CellSegmentationDataset, DeviceCachedLoader
@@ -848,7 +861,7 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
     metrics = evaluate_model(model, loader, device, threshold=threshold, object_metrics=object_metrics,
                              connectivity=connectivity, min_object_area=min_object_area,
                              probability_metrics=probability_metrics, calibration_bins=calibration_bins,
-                             probability_table=probability_table)
+                             probability_table=probability_table, **tta_kw)
     print(format_metric_report(metrics, model_name=model_name))
     return metrics
 

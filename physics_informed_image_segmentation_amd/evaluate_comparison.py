@@ -84,15 +84,19 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
                          device: torch.device, batch_size: int = 8, threshold: float = 0.5,
                          output_dir: Optional[Path] = None, device_cache: bool = False,
                          object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0,
-                         probability_metrics: bool = False, calibration_bins: int = 16) -> Dict:
+                         probability_metrics: bool = False, calibration_bins: int = 16,
+                         tta: Optional[str] = None, tta_tile: int = 512, tta_overlap: int = 64) -> Dict:
     """``probability_metrics=True`` adds the six probability-level columns and rows and writes, per
     model, threshold_sweep_<model>_<ts>.csv (the pooled curves, 1024 rows) and
     reliability_<model>_<ts>.csv (``calibration_bins`` rows); the pooled best thresholds go into
-    the comparison JSON under "pooled_best_threshold"."""
+    the comparison JSON under "pooled_best_threshold". ``tta`` ("flip" or "d4") evaluates both
+    models under test-time augmentation (``evaluate_model``); files and columns do not change."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
     obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
+    if tta is not None:
+        obj.update(tta=tta, tta_tile=tta_tile, tta_overlap=tta_overlap)
     pooled = {"baseline": ProbabilityTable(), "pde": ProbabilityTable()} if probability_metrics else {}
     prob = {tag: dict(probability_metrics=True, calibration_bins=calibration_bins, probability_table=tab)
             for tag, tab in pooled.items()}
@@ -157,13 +161,17 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
                              test_json: Path, device: torch.device, batch_size: int = 8, threshold: float = 0.5,
                              output_dir: Optional[Path] = None, device_cache: bool = False,
                              object_metrics: bool = False, connectivity: int = 8, min_object_area: int = 0,
-                             probability_metrics: bool = False, calibration_bins: int = 16) -> Dict:
+                             probability_metrics: bool = False, calibration_bins: int = 16,
+                             tta: Optional[str] = None, tta_tile: int = 512, tta_overlap: int = 64) -> Dict:
     """``probability_metrics=True`` adds the six per-image probability-level arrays to the pooled
-    statistics (the per-model sweep and reliability files belong to ``evaluate_and_compare``)."""
+    statistics (the per-model sweep and reliability files belong to ``evaluate_and_compare``).
+    ``tta`` as ``evaluate_and_compare``."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
     obj = dict(object_metrics=object_metrics, connectivity=connectivity, min_object_area=min_object_area)
+    if tta is not None:
+        obj.update(tta=tta, tta_tile=tta_tile, tta_overlap=tta_overlap)
     if probability_metrics:
         obj.update(probability_metrics=True, calibration_bins=calibration_bins)
     metric_keys = (METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
