@@ -233,7 +233,19 @@ int pis_version(void);
                                     (+10 %); 2: four histograms per block (equal); 4: one LDS atomic per pixel,
                                     no merging (+15-25 % on constant and saturated fields). Measured in
                                     profiles/probability_metrics.txt by tools/bench_probability.py */
-#define PIS_TUNE_NKEYS 53
+#define PIS_TUNE_DIRECT_MFMA16 53 /* the MFMA shape of the direct fp16x3 kernels (csrc/direct.hip), a bit set; a set
+                                     bit = v_mfma_f32_16x16x32_f16, on which the chip holds a higher clock than on
+                                     32x32x16 at equal cycles per FLOP. Bit 0: forward / pooled forward / input
+                                     gradient (a K = 32 step spans two taps of a 16-channel chunk, the ninth tap
+                                     takes 2 MFMAs: 14 per 16 x 16 tile and chunk against 13.5; set:
+                                     conv3x3_h3_kernel<...>, clear: conv3x3_h3_alt_kernel<...>). Bit 1: the 2-row
+                                     weight gradient (one K = 32 step per 32-pixel tile row; set:
+                                     conv3x3_wgrad_h3r_kernel<2>, clear: conv3x3_wgrad_h3r_alt_kernel<2>). Default 3:
+                                     -3..-8 % per launch, C2 step 20.70 -> 20.17 ms in one process
+                                     (profiles/mfma16_direct_ab.txt). Same weight planes, slabs and workspaces for
+                                     every value (the key may change between any two calls); the sums differ by
+                                     their grouping only (all fp32-class against float64) */
+#define PIS_TUNE_NKEYS 54
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,

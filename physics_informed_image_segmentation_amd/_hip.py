@@ -20,7 +20,8 @@ PIS_RELU, PIS_SCALE, PIS_MASK, PIS_ACCUMULATE, PIS_WINO_PREPARED, PIS_W_UNFLIPPE
 PIS_FILTER_READY = 64
 PIS_LOSS_ALL_TERMS, PIS_LOSS_CHAIN_SIGMOID, PIS_LOSS_NO_REACTION = 1, 2, 4
 PIS_TUNE_LAST_WGRAD_MAIN = 42  # include/pis_capi.h: host schedule knob (unet.py)
-PIS_TUNE_PROB_VARIANT = 52  # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
+PIS_TUNE_DIRECT_MFMA16 = 53  # include/pis_capi.h: MFMA shape of the direct fp16x3 kernels (bit 0 forward / input gradient, bit 1 weight gradient)
+PIS_TUNE_PROB_VARIANT = 52 # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
 LOSS_NTERMS = 8
