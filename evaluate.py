@@ -58,7 +58,24 @@ def parse_args(argv=None):
     ap.add_argument("--tta", choices=["flip", "d4"], default=None,
                     help="evaluate both models under test-time augmentation: average the predictions over the 4 "
                          "flips or all 8 symmetries of the grid (tiled prediction on the GPU; default: off)")
-    return ap.parse_args(argv)
+    from physics_informed_image_segmentation_amd.pde import add_refine_flags, refine_from_args
+    add_refine_flags(ap)
+    ap.add_argument("--physics-metrics", action="store_true",
+                    help="also report per-image physics quantities of the (refined) predictions: the mean squared "
+                         "reaction-diffusion residual, the mean phase-field energy and the interface pixel fraction")
+    ap.add_argument("--physics-diffusion", type=float, default=1.0, metavar="F",
+                    help="diffusion coefficient of the residual for --physics-metrics (default: 1.0)")
+    ap.add_argument("--physics-threshold-a", type=float, default=0.5, metavar="F",
+                    help="reaction threshold a of the residual for --physics-metrics, in (0, 1) (default: 0.5)")
+    ap.add_argument("--physics-epsilon", type=float, default=0.05, metavar="F",
+                    help="interface width of the phase-field energy for --physics-metrics (default: 0.05)")
+    args = ap.parse_args(argv)
+    args.refine_preset = refine_from_args(ap, args)
+    if args.physics_metrics and not (args.physics_diffusion >= 0 and 0 < args.physics_threshold_a < 1
+                                     and args.physics_epsilon > 0):
+        ap.error("--physics-metrics: --physics-diffusion >= 0, --physics-threshold-a in (0, 1) and "
+                 "--physics-epsilon > 0 are needed")
+    return args
 
 
 def main(argv=None):
@@ -80,6 +97,11 @@ def main(argv=None):
         common.update(probability_metrics=True, calibration_bins=args.calibration_bins)
     if args.tta:
         common["tta"] = args.tta
+    if args.refine_preset is not None:
+        common["refine"] = args.refine_preset
+    if args.physics_metrics:
+        common.update(physics_metrics=True, physics_D=args.physics_diffusion, physics_a=args.physics_threshold_a,
+                      physics_eps=args.physics_epsilon)
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

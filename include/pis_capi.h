@@ -245,7 +245,15 @@ int pis_version(void);
                                      (profiles/mfma16_direct_ab.txt). Same weight planes, slabs and workspaces for
                                      every value (the key may change between any two calls); the sums differ by
                                      their grouping only (all fp32-class against float64) */
-#define PIS_TUNE_NKEYS 54
+#define PIS_TUNE_EVOLVE_T 54 /* pis_pde_evolve (csrc/evolve.hip): T, the explicit steps one launch advances inside
+                                LDS (temporal blocking): 1, 2, 4 or 8, anything else is PIS_ERR_ARG. Every value
+                                gives the same bits; 1 is the one-step-per-launch form. Default 8: the lowest
+                                64-step time at 8 x 512^2 with mu = 0, 206.7 us against 267.7 (T = 4), 414.1
+                                (T = 2) and 705.7 (T = 1); with the u0 plane staged (mu != 0) T = 4 is 17 %
+                                faster there and 2 % slower at 2048^2 (tools/bench_evolve.py,
+                                profiles/pde_evolve.txt). The key may change between any two calls (the
+                                workspace does not depend on it) */
+#define PIS_TUNE_NKEYS 55
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -781,6 +789,59 @@ int pis_tile_gather(const void* src, int src_fmt, size_t src_stride, const float
                     pis_stream_t stream);
 int pis_tile_blend(const float* u, int S, int H, int W, int th, int tw, int ov, int sym_mask, float thr,
                    float* prob, uint8_t* mask, pis_stream_t stream);
+
+/* ---- PDE evolution of a probability map, and the physics quantities of one (no reference counterpart;
+ * pde.py:evolve_np / energies_np restate both in float32 numpy and agree bit for bit) ----
+ * Maps are (B, H, W) fp32 contiguous, 2 <= H, W <= 4096, no divisibility requirement. With
+ * p = the map padded by one pixel under reflect(i, n) of pis_cache_batch_affine (no repeated edge) and
+ *   up, dn, lf, rt = p[y-1][x], p[y+1][x], p[y][x-1], p[y][x+1]
+ * every operation below is float32 and correctly rounded on its own (no fused multiply-add):
+ *   lap = ((up + dn) + (lf + rt)) - 4 c
+ *   r   = (c (1 - c)) (c - a)
+ *
+ * pis_pde_evolve: `steps` explicit Euler steps of u_t = D lap(u) + k u (1 - u) (u - a) + mu (u0 - u), per step
+ *   t  = D lap;  t = t + k r;  if mu != 0: t = t + mu (u0 - c)         u0 NULL: the input map u
+ *   c' = c + dt t;  with PIS_EVOLVE_CLAMP: c' = c' < 0 ? 0 : c', then c' = c' > 1 ? 1 : c'
+ * The pairing (up + dn) + (lf + rt) is part of the definition: each pair commutes, so a step commutes bit
+ * for bit with an H flip, a W flip and a transpose, and the reflect extension of a map evolves to the reflect
+ * extension of the evolved map. The kernel relies on it: a launch advances up to T steps (pis_tune key
+ * PIS_TUNE_EVOLVE_T) on PIS_EVOLVE_TILE_H x PIS_EVOLVE_TILE_W tiles whose T-wide halo is loaded once through
+ * reflect (any number of periods) and never exchanged. ceil(steps / T) launches on `stream`, chained through
+ * at most two scratch maps in ws (16-byte aligned, pis_pde_evolve_ws(B, H, W, steps) bytes; fewer than three
+ * launches need less, and none is read by the launch that writes it); the last launch writes out and, when
+ * mask is not NULL, mask (B, H, W) uint8 = (c > thr), strict. steps == 0 copies u to out (and writes mask). u and
+ * u0 are not written. No host synchronisation; capturable in a graph.
+ * PIS_ERR_ARG before any GPU work: u or out NULL; B < 1; H or W outside [2, 4096]; steps outside
+ * [0, PIS_EVOLVE_MAX_STEPS]; unknown flags; D < 0, k < 0, mu < 0, a outside (0, 1), dt <= 0 or
+ * dt (4 D + k + mu) > 1 (in float64: under that bound the step is monotone in every argument, so [0, 1] is
+ * invariant in exact arithmetic and the clamp only removes rounding excursions); NaN scalars; u, u0, out or ws
+ * not 16-byte aligned, mask not 4-byte aligned; out overlapping u or u0; ws missing, too small, or overlapping
+ * a map; a tune key that holds no legal T. pis_pde_evolve_ws answers 0 (and sets the message) for a shape or
+ * step count outside these bounds.
+ *
+ * pis_pde_energies: per image s, out_f64[s][0] = rd, out_f64[s][1] = pf, out_i64[s] = interface:
+ *   rd        = (sum over pixels of double(res)^2) / (H W),   res = D lap + r
+ *   pf        = (sum over pixels of double(e)) / (H W),       gx = 0.5 (rt - lf), gy = 0.5 (dn - up),
+ *               g = gx gx + gy gy, w = (c c) ((1 - c) (1 - c)), e = he g + ie w, he = eps / 2, ie = 1 / eps in fp32
+ *   interface = the number of pixels with 0.1f < c < 0.9f
+ * Two launches: row bands write float64 partial sums and int64 counts into ws (8-byte aligned,
+ * pis_pde_energies_ws(B, H, W) bytes), a second launch adds them per image in a fixed order; no floating-point
+ * atomics, so the result is bitwise equal from run to run. The float32 per-pixel values are the definition's;
+ * only the order of the float64 sum differs from a host sum (relative (n - 1) 2^-53 at most: the terms are
+ * non-negative).
+ * PIS_ERR_ARG: a NULL pointer; a shape outside the bounds above; D < 0, a outside (0, 1), eps <= 0; out_f64,
+ * out_i64 or ws not 8-byte aligned; ws missing or too small. */
+#define PIS_EVOLVE_CLAMP 1
+#define PIS_EVOLVE_TILE_H 32
+#define PIS_EVOLVE_TILE_W 64
+#define PIS_EVOLVE_MAX_STEPS 65536
+size_t pis_pde_evolve_ws(int B, int H, int W, int steps);
+int pis_pde_evolve(const float* u, const float* u0, float* out, uint8_t* mask, int B, int H, int W, float D, float k,
+                   float a, float mu, float dt, int steps, int flags, float thr, void* ws, size_t ws_bytes,
+                   pis_stream_t stream);
+size_t pis_pde_energies_ws(int B, int H, int W);
+int pis_pde_energies(const float* u, int B, int H, int W, float D, float a, float eps, double* out_f64,
+                     int64_t* out_i64, void* ws, size_t ws_bytes, pis_stream_t stream);
 
 #ifdef __cplusplus
 }

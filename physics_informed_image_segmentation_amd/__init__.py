@@ -23,7 +23,8 @@ from .evaluate import (ProbabilityTable, best_threshold_batch, boundary_counts, 
 from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
-from .pde import PDERegularization, create_pde_regularization  # noqa: E402
+from .pde import (PDERefine, PDERegularization, create_pde_regularization, energies, energies_np, evolve,  # noqa: E402
+                  evolve_np)
 from .train import EarlyStopping, train, train_epoch, train_stage, validate  # noqa: E402
 from .unet import UNet, count_parameters  # noqa: E402
 from .evaluate_comparison import evaluate_and_compare, run_repeated_evaluations  # noqa: E402
@@ -42,4 +43,5 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "AffineAugment", "object_counts", "label_components", "compute_object_f1_batch", "compute_aji_batch",
            "probability_table", "threshold_sweep_counts", "compute_auroc_batch", "compute_average_precision_batch",
            "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable",
-           "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np"]
+           "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np",
+           "PDERefine", "evolve", "evolve_np", "energies", "energies_np"]

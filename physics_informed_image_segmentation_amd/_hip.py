@@ -22,6 +22,8 @@ PIS_LOSS_ALL_TERMS, PIS_LOSS_CHAIN_SIGMOID, PIS_LOSS_NO_REACTION = 1, 2, 4
 PIS_TUNE_LAST_WGRAD_MAIN = 42  # include/pis_capi.h: host schedule knob (unet.py)
 PIS_TUNE_DIRECT_MFMA16 = 53  # include/pis_capi.h: MFMA shape of the direct fp16x3 kernels (bit 0 forward / input gradient, bit 1 weight gradient)
 PIS_TUNE_PROB_VARIANT = 52 # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
+PIS_TUNE_EVOLVE_T = 54  # include/pis_capi.h: steps per launch of pis_pde_evolve (1, 2, 4 or 8)
+PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
 LOSS_NTERMS = 8
@@ -116,6 +118,11 @@ _SIGNATURES = {
     "pis_tile_count": ([I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
     "pis_tile_gather": ([P, I, Z, P, I, I, I, I, I, I, I, L, L, P, P], c_int),
     "pis_tile_blend": ([P, I, I, I, I, I, I, I, c_float, P, P, P], c_int),
+    "pis_pde_evolve_ws": ([I, I, I, I], c_size_t),
+    "pis_pde_evolve": ([P, P, P, P, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, c_float, P, Z, P],
+                       c_int),
+    "pis_pde_energies_ws": ([I, I, I], c_size_t),
+    "pis_pde_energies": ([P, I, I, I, c_float, c_float, c_float, P, P, P, Z, P], c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -683,6 +683,20 @@ _probability_table_of_batch = probability_table  # evaluate_model has a paramete
 # the per-image arrays evaluate_model(probability_metrics=True) adds, in this order
 PROBABILITY_METRIC_KEYS = ("auroc_scores", "average_precision_scores", "ece_scores", "brier_scores",
                            "best_threshold_dice_scores", "best_thresholds")
+# the per-image arrays evaluate_model(physics_metrics=True) adds, in this order
+PHYSICS_METRIC_KEYS = ("rd_residuals", "pf_energies", "interface_fractions")
+
+
+def _check_refine(refine) -> None:
+    from .pde import PDERefine
+    if refine is not None and not isinstance(refine, PDERefine):
+        raise TypeError(f"refine must be a pde.PDERefine or None, got {type(refine).__name__}")
+
+
+def _check_physics(D: float, a: float, eps: float) -> None:
+    if not (D >= 0 and 0 < a < 1 and eps > 0):
+        raise ValueError(f"physics_D = {D}, physics_a = {a}, physics_eps = {eps}: D >= 0, 0 < a < 1 and eps > 0 "
+                         "are needed")
 
 
 @torch.no_grad()
@@ -691,7 +705,9 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
                    min_object_area: int = 0, object_backend: str = "auto", probability_metrics: bool = False,
                    calibration_bins: int = 16, probability_backend: str = "auto",
                    probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
-                   tta_tile: int = 512, tta_overlap: int = 64) -> Dict[str, np.ndarray]:
+                   tta_tile: int = 512, tta_overlap: int = 64, refine=None, physics_metrics: bool = False,
+                   physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05
+                   ) -> Dict[str, np.ndarray]:
     """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
     (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
     ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
@@ -704,8 +720,19 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     ``probability_table`` is updated with every batch (the pooled curves of the loader).
     ``tta="flip"`` / ``"d4"``: the outputs are the test-time-augmented probabilities of a
     ``predict.Predictor`` (tiles of at most ``tta_tile`` with ``tta_overlap`` overlap, 4 or 8
-    symmetries) instead of ``model(images)``; everything downstream is unchanged."""
+    symmetries) instead of ``model(images)``; everything downstream is unchanged.
+    ``refine`` (a ``pde.PDERefine``): every batch's probabilities (after the blend, with ``tta``)
+    are evolved under the PDE (``pde.evolve``) before the threshold and before every metric family.
+    ``physics_metrics=True`` adds ``rd_residuals`` (per-image mean squared reaction-diffusion
+    residual, with ``physics_D`` and ``physics_a``), ``pf_energies`` (per-image mean phase-field
+    energy density, ``physics_eps``) and ``interface_fractions`` (the share of pixels with
+    0.1 < u < 0.9) from one ``pde.energies`` call and one device->host copy per batch."""
     predictor = None
+    _check_refine(refine)  # both refused before any GPU work
+    if physics_metrics:
+        _check_physics(physics_D, physics_a, physics_eps)
+    if refine is not None or physics_metrics:
+        from .pde import energies as _energies, evolve as _evolve
     if tta is not None:  # refused before any GPU work
         from .predict import Predictor
         if tta not in ("flip", "d4"):
@@ -721,9 +748,12 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     dice, iou, bf1, hd = [], [], [], []
     of1, aji, cerr = [], [], []
     prob = [[] for _ in range(6)]
+    phys = [[] for _ in range(3)]
     for images, masks in dataloader:
         images, masks = images.to(device, non_blocking=True), masks.to(device, non_blocking=True)
         outputs = model(images) if predictor is None else predictor.predict_batch(images)[0]
+        if refine is not None:
+            outputs = _evolve(outputs, refine)
         _, scores = sample_counts(outputs, masks, threshold)
         s = scores.cpu().numpy()
         dice.extend(s[:, 0].tolist())
@@ -758,6 +788,12 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
                                thr_dice, thr]).cpu().numpy()
             for acc, row in zip(prob, six):
                 acc.extend(row.tolist())
+        if physics_metrics:
+            e, n = _energies(outputs, physics_D, physics_a, physics_eps)
+            px = float(outputs.shape[-2] * outputs.shape[-1])
+            three = torch.stack([e[:, 0], e[:, 1], n.to(torch.float64) / px]).cpu().numpy()
+            for acc, row in zip(phys, three):
+                acc.extend(row.tolist())
     out = {"dice_scores": np.array(dice), "iou_scores": np.array(iou)}
     if boundary_metrics:
         out["boundary_f1_scores"] = np.array(bf1)
@@ -768,6 +804,9 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
         out["object_count_errors"] = np.array(cerr)
     if probability_metrics:
         for key, acc in zip(PROBABILITY_METRIC_KEYS, prob):
+            out[key] = np.array(acc, dtype=np.float64)
+    if physics_metrics:
+        for key, acc in zip(PHYSICS_METRIC_KEYS, phys):
             out[key] = np.array(acc, dtype=np.float64)
     return out
 
@@ -829,17 +868,27 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
                          connectivity: int = 8, min_object_area: int = 0, probability_metrics: bool = False,
                          calibration_bins: int = 16,
                          probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
-                         tta_tile: int = 512, tta_overlap: int = 64) -> Dict[str, np.ndarray]:
+                         tta_tile: int = 512, tta_overlap: int = 64, refine=None, physics_metrics: bool = False,
+                         physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05
+                         ) -> Dict[str, np.ndarray]:
     """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
     ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
     (``dataset.DeviceCachedLoader``) instead of ``DataLoader`` workers; a set that does not fit
     falls back to them. ``object_metrics=True`` adds the object-level arrays of ``evaluate_model``,
     ``probability_metrics=True`` its probability-level arrays (ECE over ``calibration_bins`` bins;
     a ``ProbabilityTable`` passed as ``probability_table`` receives the pooled table of the set).
-    ``tta``, ``tta_tile``, ``tta_overlap``: test-time augmentation, as ``evaluate_model``."""
+    ``tta``, ``tta_tile``, ``tta_overlap``: test-time augmentation, as ``evaluate_model``.
+    ``refine``, ``physics_metrics``, ``physics_D``, ``physics_a``, ``physics_eps``: PDE refinement
+    of the probabilities and the per-image physics arrays, as ``evaluate_model``."""
     if probability_metrics:
         _check_calibration_bins(calibration_bins)
+    _check_refine(refine)
     tta_kw = {} if tta is None else dict(tta=tta, tta_tile=tta_tile, tta_overlap=tta_overlap)
+    if refine is not None:
+        tta_kw["refine"] = refine
+    if physics_metrics:
+        _check_physics(physics_D, physics_a, physics_eps)
+        tta_kw.update(physics_metrics=True, physics_D=physics_D, physics_a=physics_a, physics_eps=physics_eps)
     from torch.utils.data import DataLoader
 
     from .dataset import CellSegmentationDataset, DeviceCachedLoader
@@ -873,4 +922,4 @@ __all__ = ["compute_iou", "compute_iou_batch", "extract_boundaries", "compute_bo
            "format_metric_report", "evaluate_on_test_set", "object_counts", "label_components",
            "compute_object_f1_batch", "compute_aji_batch", "probability_table", "threshold_sweep_counts",
            "compute_auroc_batch", "compute_average_precision_batch", "compute_ece_batch", "compute_brier_batch",
-           "best_threshold_batch", "ProbabilityTable"]
+           "best_threshold_batch", "ProbabilityTable", "PHYSICS_METRIC_KEYS"]

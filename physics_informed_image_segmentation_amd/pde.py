@@ -8,9 +8,21 @@ per-pixel field helpers (``compute_laplacian``, ``reaction_term``,
 ``compute_residual``, ``compute_gradient_magnitude``, :49-178) are one HIP
 stencil kernel each way (``pis_pde_fields`` / ``pis_pde_fields_bwd``) and are
 differentiable, like the reference's F.pad + F.conv2d compositions.
+
+Running the PDE (no reference counterpart): ``evolve`` advances a probability map
+under ``u_t = D lap(u) + k u (1 - u) (u - a) + mu (u0 - u)`` by explicit Euler steps
+(``pis_pde_evolve``: several steps per launch inside LDS), ``energies`` gives the per-image
+residual, phase-field energy and interface pixel count (``pis_pde_energies``). ``evolve_np`` and
+``energies_np`` are their definitions of record in float32 numpy, operation for operation; the
+kernels agree with them bit for bit (tests/test_evolve_gpu.py).
 """
 from __future__ import annotations
 
+import ctypes
+from dataclasses import dataclass
+from typing import Optional, Tuple, Union
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -18,6 +30,287 @@ from . import _hip
 from .fused import LossConfig, fused_loss
 
 _LAP, _RES, _GM = 0, 1, 2
+
+
+# the output tile of a pis_pde_evolve block and the legal values of its temporal block T
+EVOLVE_TILE = (_hip.PIS_EVOLVE_TILE_H, _hip.PIS_EVOLVE_TILE_W)
+EVOLVE_T_VALUES = (1, 2, 4, 8)
+EVOLVE_MAX_STEPS, EVOLVE_MAX_SIDE = _hip.PIS_EVOLVE_MAX_STEPS, 4096
+_f32 = np.float32
+
+
+def evolve_temporal_block(value: Optional[int] = None) -> int:
+    """The steps one ``pis_pde_evolve`` launch advances (pis_tune key ``PIS_TUNE_EVOLVE_T``); with
+    ``value`` (one of ``EVOLVE_T_VALUES``) it is set, and the previous value returned. Every value
+    gives the same bits."""
+    if value is not None and value not in EVOLVE_T_VALUES:
+        raise ValueError(f"temporal block {value!r}: one of {EVOLVE_T_VALUES} is needed")
+    return int(_hip.lib().pis_tune(_hip.PIS_TUNE_EVOLVE_T, -1 if value is None else int(value)))
+
+
+def _check_evolve(steps, D, k, a, mu, dt) -> Tuple[int, np.float32, np.float32, np.float32, np.float32, np.float32]:
+    """The stability check of ``pis_pde_evolve``, on the float32 scalars it receives; fills in
+    ``dt=None``. Raises ValueError."""
+    if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= EVOLVE_MAX_STEPS:
+        raise ValueError(f"steps = {steps!r}: an integer in [0, {EVOLVE_MAX_STEPS}] is needed")
+    D, k, a, mu = _f32(D), _f32(k), _f32(a), _f32(mu)
+    if not (D >= 0 and k >= 0 and mu >= 0):
+        raise ValueError(f"D = {D}, k = {k}, mu = {mu}: none may be negative")
+    if not 0 < a < 1:
+        raise ValueError(f"a = {a}: the reaction threshold must lie in (0, 1)")
+    rate = float(4.0 * float(D) + float(k) + float(mu))
+    if dt is None:
+        if rate <= 0:
+            raise ValueError("dt=None needs 4 D + k + mu > 0")
+        dt = _f32(0.5) / _f32(_f32(_f32(4) * D + k) + mu)  # half the monotonicity bound: a choice
+    dt = _f32(dt)
+    if not dt > 0:
+        raise ValueError(f"dt = {dt}: a positive step is needed")
+    if not float(dt) * rate <= 1.0:
+        raise ValueError(f"dt (4 D + k + mu) = {float(dt) * rate:g} exceeds 1: the explicit step is not monotone "
+                         f"(dt <= {1.0 / rate:g} is needed)")
+    return int(steps), D, k, a, mu, dt
+
+
+def _maps_np(u, what: str) -> np.ndarray:
+    u = np.asarray(u)
+    if u.dtype != np.float32:
+        raise TypeError(f"{what}: float32 maps expected, got {u.dtype}")
+    if u.ndim == 4 and u.shape[1] == 1:
+        u = u[:, 0]
+    if u.ndim != 3:
+        raise ValueError(f"{what}: (B, H, W) or (B, 1, H, W) expected, got {u.shape}")
+    if u.shape[0] < 1 or not (2 <= u.shape[1] <= EVOLVE_MAX_SIDE and 2 <= u.shape[2] <= EVOLVE_MAX_SIDE):
+        raise ValueError(f"{what}: B >= 1 and 2 <= H, W <= {EVOLVE_MAX_SIDE} are needed, got {u.shape}")
+    return u
+
+
+def _neighbours_np(c: np.ndarray):
+    p = np.pad(c, ((0, 0), (1, 1), (1, 1)), mode="reflect")
+    return p[:, :-2, 1:-1], p[:, 2:, 1:-1], p[:, 1:-1, :-2], p[:, 1:-1, 2:]  # up, dn, lf, rt
+
+
+def evolve_np(u, steps: int, D, k, a, mu=0.0, dt=None, clamp: bool = True, u0=None) -> np.ndarray:
+    """The definition of ``evolve``: ``steps`` explicit Euler steps of
+    ``u_t = D lap(u) + k u (1 - u) (u - a) + mu (u0 - u)`` on float32 maps ``u`` ((B, H, W) or
+    (B, 1, H, W), H, W >= 2), every scalar a float32 and every operation rounded on its own. Per
+    step, with ``c`` the current map and up / dn / lf / rt its reflect-padded neighbours::
+
+        lap = ((up + dn) + (lf + rt)) - 4 c
+        r   = (c (1 - c)) (c - a)
+        t   = D lap;  t = t + k r;  if mu != 0: t = t + mu (u0 - c)
+        c'  = c + dt t;  if clamp: c' = min(max(c', 0), 1)
+
+    ``u0`` is the initial map unless given. The pairing ``(up + dn) + (lf + rt)`` is part of the
+    definition: each pair commutes, so a step commutes bit for bit with an H flip, a W flip and a
+    transpose. ``dt=None`` is ``float32(0.5) / float32(4 D + k + mu)``. Refused with ValueError:
+    negative D, k or mu, ``a`` outside (0, 1), ``dt <= 0`` and ``dt (4 D + k + mu) > 1``; under
+    that bound the update is monotone in every argument (f' >= -1 on [0, 1] for
+    f = u (1 - u) (u - a)), so [0, 1] is invariant in exact arithmetic and ``clamp`` only removes
+    rounding excursions."""
+    steps, D, k, a, mu, dt = _check_evolve(steps, D, k, a, mu, dt)
+    shape = np.shape(u)
+    c = _maps_np(u, "evolve_np").copy()
+    z = c if u0 is None else _maps_np(u0, "evolve_np: u0")
+    if z.shape != c.shape:
+        raise ValueError(f"evolve_np: u0 {z.shape} does not match u {c.shape}")
+    z = z.copy()
+    one, four, zero = _f32(1), _f32(4), _f32(0)
+    with np.errstate(all="ignore"):
+        for _ in range(steps):
+            up, dn, lf, rt = _neighbours_np(c)
+            lap = ((up + dn) + (lf + rt)) - four * c
+            r = (c * (one - c)) * (c - a)
+            t = D * lap
+            t = t + k * r
+            if mu != 0:
+                t = t + mu * (z - c)
+            n = c + dt * t
+            if clamp:
+                n = np.where(n < zero, zero, n)
+                n = np.where(n > one, one, n)
+            c = n.astype(np.float32, copy=False)
+    return c.reshape(shape)
+
+
+def energies_np(u, D, a, eps) -> Tuple[np.ndarray, np.ndarray]:
+    """The definition of ``energies``: per image of float32 maps ``u``, ``(out (B, 2) float64,
+    interface (B,) int64)`` with ``out[:, 0]`` the mean of ``double(res)^2``,
+    ``res = D lap + (c (1 - c)) (c - a)``, ``out[:, 1]`` the mean of ``double(e)``,
+    ``e = he (gx gx + gy gy) + ie ((c c) ((1 - c) (1 - c)))`` with ``gx = 0.5 (rt - lf)``,
+    ``gy = 0.5 (dn - up)``, ``he = float32(eps) / 2``, ``ie = 1 / float32(eps)``, and ``interface``
+    the count of pixels with ``float32(0.1) < c < float32(0.9)``. The field arithmetic is float32,
+    every operation rounded on its own; the sums are float64."""
+    D, a, eps = _f32(D), _f32(a), _f32(eps)
+    if not (D >= 0 and 0 < a < 1 and eps > 0):
+        raise ValueError(f"D = {D}, a = {a}, eps = {eps}: D >= 0, 0 < a < 1 and eps > 0 are needed")
+    c = _maps_np(u, "energies_np")
+    one, four, half = _f32(1), _f32(4), _f32(0.5)
+    he, ie = eps / _f32(2), one / eps
+    with np.errstate(all="ignore"):
+        up, dn, lf, rt = _neighbours_np(c)
+        lap = ((up + dn) + (lf + rt)) - four * c
+        res = D * lap + (c * (one - c)) * (c - a)
+        gx, gy = half * (rt - lf), half * (dn - up)
+        g = gx * gx + gy * gy
+        w = (c * c) * ((one - c) * (one - c))
+        e = he * g + ie * w
+        assert res.dtype == np.float32 and e.dtype == np.float32
+        out = np.stack([(res.astype(np.float64) ** 2).mean(axis=(1, 2)), e.astype(np.float64).mean(axis=(1, 2))], axis=1)
+        interface = ((c > _f32(0.1)) & (c < _f32(0.9))).sum(axis=(1, 2)).astype(np.int64)
+    return out, interface
+
+
+@dataclass(frozen=True)
+class PDERefine:
+    """The arguments of one ``evolve`` call: a preset for ``Predictor(refine=...)`` and
+    ``evaluate_model(refine=...)``. ``dt=None``: ``float32(0.5) / float32(4 D + k + mu)``."""
+    steps: int
+    D: float
+    k: float
+    a: float
+    mu: float = 0.0
+    dt: Optional[float] = None
+    clamp: bool = True
+
+    def __post_init__(self):
+        _check_evolve(self.steps, self.D, self.k, self.a, self.mu, self.dt)
+
+    @classmethod
+    def reaction_diffusion(cls, steps: int, diffusion_coeff: float = 1.0, reaction_threshold: float = 0.5,
+                           mu: float = 0.0, dt: Optional[float] = None) -> "PDERefine":
+        """``u_t = D lap(u) + u (1 - u) (u - a)``: the PDE whose residual the loss penalises
+        (``PDERegularization.compute_loss``): D = ``diffusion_coeff``, k = 1, a = ``reaction_threshold``."""
+        return cls(steps=steps, D=diffusion_coeff, k=1.0, a=reaction_threshold, mu=mu, dt=dt)
+
+    @classmethod
+    def phase_field(cls, steps: int, epsilon: float = 0.05, mu: float = 0.0, dt: Optional[float] = None
+                    ) -> "PDERefine":
+        """The Allen-Cahn flow of the phase-field energy ``(eps / 2) |grad u|^2 + (1 / eps) u^2 (1 - u)^2``:
+        ``u_t = eps lap(u) - (1 / eps) 2 u (1 - u) (1 - 2 u) = eps lap(u) + (4 / eps) u (1 - u) (u - 1/2)``,
+        so D = eps, k = 4 / eps, a = 1/2. It is discretised with the 5-point Laplacian and is therefore
+        NOT the exact discrete gradient of the loss's energy, whose gradient term uses central
+        differences (their adjoint is a wider, 2-pixel-stride Laplacian)."""
+        if not epsilon > 0:
+            raise ValueError("epsilon must be positive")
+        return cls(steps=steps, D=epsilon, k=4.0 / epsilon, a=0.5, mu=mu, dt=dt)
+
+    def kwargs(self) -> dict:
+        return dict(steps=self.steps, D=self.D, k=self.k, a=self.a, mu=self.mu, dt=self.dt, clamp=self.clamp)
+
+
+def add_refine_flags(ap):
+    """--refine and its parameters on an argparse parser: shared by predict.py and evaluate.py."""
+    ap.add_argument("--refine", choices=["rd", "pf"], default=None,
+                    help="evolve the predicted probabilities under a PDE before the threshold: rd = the "
+                         "reaction-diffusion equation the loss penalises, pf = the Allen-Cahn flow of the "
+                         "phase-field energy (default: off)")
+    ap.add_argument("--refine-steps", type=int, default=None, metavar="N",
+                    help="explicit time steps of --refine, 0..65536 (required with --refine)")
+    ap.add_argument("--refine-dt", type=float, default=None, metavar="F",
+                    help="time step of --refine (default: half the stability bound 1 / (4 D + k + mu))")
+    ap.add_argument("--refine-mu", type=float, default=0.0, metavar="F",
+                    help="fidelity weight of --refine: pulls the evolved map back to the prediction (default: 0)")
+    ap.add_argument("--refine-diffusion", type=float, default=1.0, metavar="F",
+                    help="diffusion coefficient of --refine rd (default: 1.0)")
+    ap.add_argument("--refine-threshold-a", type=float, default=0.5, metavar="F",
+                    help="reaction threshold a of --refine rd, in (0, 1) (default: 0.5)")
+    ap.add_argument("--refine-epsilon", type=float, default=0.05, metavar="F",
+                    help="interface width of --refine pf (default: 0.05)")
+
+
+def refine_from_args(ap, args):
+    """The PDERefine of the parsed --refine flags, or None; a bad combination ends in ap.error."""
+    if args.refine is None:
+        if args.refine_steps is not None:
+            ap.error("--refine-steps needs --refine {rd,pf}")
+        return None
+    if args.refine_steps is None:
+        ap.error("--refine needs --refine-steps N")
+    try:
+        if args.refine == "rd":
+            return PDERefine.reaction_diffusion(args.refine_steps, args.refine_diffusion, args.refine_threshold_a,
+                                                mu=args.refine_mu, dt=args.refine_dt)
+        return PDERefine.phase_field(args.refine_steps, args.refine_epsilon, mu=args.refine_mu, dt=args.refine_dt)
+    except ValueError as e:
+        ap.error(f"--refine: {e}")
+
+
+def _maps_cuda(u: torch.Tensor, what: str) -> torch.Tensor:
+    _hip.require_cuda(u, what)
+    if u.dtype != torch.float32:
+        raise TypeError(f"{what}: float32 maps expected, got {u.dtype}")
+    if not (u.dim() == 3 or (u.dim() == 4 and u.shape[1] == 1)):
+        raise ValueError(f"{what}: (B, H, W) or (B, 1, H, W) expected, got {tuple(u.shape)}")
+    B, H, W = u.shape[0], u.shape[-2], u.shape[-1]
+    if B < 1 or not (2 <= H <= EVOLVE_MAX_SIDE and 2 <= W <= EVOLVE_MAX_SIDE):
+        raise ValueError(f"{what}: B >= 1 and 2 <= H, W <= {EVOLVE_MAX_SIDE} are needed, got {tuple(u.shape)}")
+    return u.detach().contiguous()
+
+
+def evolve(u: torch.Tensor, refine: Optional[PDERefine] = None, *, steps: Optional[int] = None, D=None, k=None,
+           a=None, mu=0.0, dt=None, clamp: bool = True, u0: Optional[torch.Tensor] = None,
+           threshold: Optional[float] = None) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    """``evolve_np`` on the GPU, bit for bit: ``u`` ((B, H, W) or (B, 1, H, W) float32 CUDA) advanced
+    by ``steps`` explicit steps, either under a ``PDERefine`` or under ``steps, D, k, a[, mu, dt, clamp]``.
+    Returns a new tensor of ``u``'s shape (``u`` is left unchanged), or ``(tensor, mask)`` when
+    ``threshold`` is given: ``mask = (evolved > threshold)`` as uint8, written by the same launch.
+    ``ceil(steps / T)`` launches on the current stream, no host synchronisation. NOT differentiable:
+    the input is detached and no gradient flows to it. Bad arguments raise ValueError before any
+    GPU work."""
+    if refine is not None:
+        if not isinstance(refine, PDERefine):
+            raise TypeError(f"evolve: refine must be a PDERefine, got {type(refine).__name__}")
+        if steps is not None or D is not None or k is not None or a is not None:
+            raise ValueError("evolve: give a PDERefine or steps, D, k, a, not both")
+        steps, D, k, a, mu, dt, clamp = (refine.steps, refine.D, refine.k, refine.a, refine.mu, refine.dt,
+                                         refine.clamp)
+    elif steps is None or D is None or k is None or a is None:
+        raise ValueError("evolve: a PDERefine, or steps, D, k and a, are needed")
+    steps, D, k, a, mu, dt = _check_evolve(steps, D, k, a, mu, dt)
+    if threshold is not None and not float(threshold) == float(threshold):
+        raise ValueError("evolve: threshold is NaN")
+    uc = _maps_cuda(u, "evolve")
+    B, H, W = uc.shape[0], uc.shape[-2], uc.shape[-1]
+    z = None
+    if u0 is not None:
+        z = _maps_cuda(u0, "evolve: u0")
+        if z.shape[0] != B or tuple(z.shape[-2:]) != (H, W) or z.device != uc.device:
+            raise ValueError(f"evolve: u0 {tuple(u0.shape)} does not match u {tuple(u.shape)}")
+    out = torch.empty_like(uc)
+    mask = torch.empty(uc.shape, dtype=torch.uint8, device=uc.device) if threshold is not None else None
+    with torch.cuda.device(uc.device):
+        nbytes = int(_hip.lib().pis_pde_evolve_ws(B, H, W, steps))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=uc.device)
+        f = ctypes.c_float
+        _hip.call("pis_pde_evolve", _hip.ptr(uc), _hip.ptr(z), _hip.ptr(out), _hip.ptr(mask), B, H, W, f(D), f(k), f(a),
+                  f(mu), f(dt), steps, _hip.PIS_EVOLVE_CLAMP if clamp else 0,
+                  f(0.0 if threshold is None else float(threshold)), _hip.ptr(ws), nbytes,
+                  _hip.stream_handle(uc.device))
+    out = out.reshape(u.shape)
+    return out if mask is None else (out, mask.reshape(u.shape))
+
+
+def energies(u: torch.Tensor, D=1.0, a=0.5, eps=0.05) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``energies_np`` on the GPU: ``((B, 2) float64, (B,) int64)`` on ``u``'s device, column 0 the
+    mean squared reaction-diffusion residual, column 1 the mean phase-field energy density, and
+    the count of interface pixels (0.1 < u < 0.9). The per-pixel float32 values are the
+    definition's; the float64 sums run in a fixed order (no atomics), so two runs give the same
+    bits. One ``pis_pde_energies`` call, no host synchronisation. Not differentiable."""
+    D, a, eps = _f32(D), _f32(a), _f32(eps)
+    if not (D >= 0 and 0 < a < 1 and eps > 0):
+        raise ValueError(f"D = {D}, a = {a}, eps = {eps}: D >= 0, 0 < a < 1 and eps > 0 are needed")
+    uc = _maps_cuda(u, "energies")
+    B, H, W = uc.shape[0], uc.shape[-2], uc.shape[-1]
+    out = torch.empty((B, 2), dtype=torch.float64, device=uc.device)
+    cnt = torch.empty((B,), dtype=torch.int64, device=uc.device)
+    with torch.cuda.device(uc.device):
+        nbytes = int(_hip.lib().pis_pde_energies_ws(B, H, W))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=uc.device)
+        f = ctypes.c_float
+        _hip.call("pis_pde_energies", _hip.ptr(uc), B, H, W, f(D), f(a), f(eps), _hip.ptr(out), _hip.ptr(cnt),
+                  _hip.ptr(ws), nbytes, _hip.stream_handle(uc.device))
+    return out, cnt
 
 
 class _PDEField(torch.autograd.Function):
@@ -101,6 +394,24 @@ class PDERegularization(nn.Module):
         return fused_loss(u, u.detach(), cfg)
 
 
+    # ---- running the PDE, and its per-image quantities (not differentiable) ----
+    def evolve(self, u: torch.Tensor, steps: int, dt: Optional[float] = None, mu: float = 0.0,
+               u0: Optional[torch.Tensor] = None, threshold: Optional[float] = None):
+        """``evolve`` under this module's PDE: D = ``diffusion_coeff``, k = 1, a = ``reaction_threshold``."""
+        return evolve(u, steps=steps, D=self.diffusion_coeff, k=1.0, a=self.reaction_threshold, mu=mu, dt=dt, u0=u0,
+                      threshold=threshold)
+
+    def energies(self, u: torch.Tensor, epsilon: float = 0.05) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``energies`` with this module's D and a: per image, the quantities whose batch means are
+        ``compute_loss`` and ``compute_phase_field_loss``, and the interface pixel count."""
+        return energies(u, self.diffusion_coeff, self.reaction_threshold, epsilon)
+
+
 def create_pde_regularization(diffusion_coeff: float = 1.0, reaction_threshold: float = 0.5) -> PDERegularization:
     """src/pde.py:215-232."""
     return PDERegularization(diffusion_coeff=diffusion_coeff, reaction_threshold=reaction_threshold)
+
+
+__all__ = ["PDERegularization", "create_pde_regularization", "PDERefine", "evolve", "evolve_np", "energies",
+           "energies_np", "evolve_temporal_block", "EVOLVE_TILE", "EVOLVE_T_VALUES", "add_refine_flags",
+           "refine_from_args"]

@@ -303,10 +303,12 @@ class Predictor:
     ``pis_tile_gather`` and one forward per chunk of ``batch_tiles`` jobs, one ``pis_tile_blend``
     at the end; no call synchronises with the host. The tile outputs of all jobs are held in one
     buffer; a buffer above ``max_workspace_bytes`` (default 8 GiB: a choice, not a measurement) is
-    refused before any GPU work."""
+    refused before any GPU work. ``refine`` (a ``pde.PDERefine``): the blended whole-image
+    probabilities are evolved under the PDE (``pde.evolve``, any H and W) and the mask returned is
+    the one the evolve launch wrote, ``refined > threshold``."""
 
     def __init__(self, model, tile: int = 512, overlap: int = 64, tta: Optional[str] = None, batch_tiles: int = 8,
-                 threshold: float = 0.5, max_workspace_bytes: int = 8 << 30):
+                 threshold: float = 0.5, max_workspace_bytes: int = 8 << 30, refine=None):
         if tta not in (None, "flip", "d4"):
             raise ValueError(f"tta must be None, 'flip' or 'd4', got {tta!r}")
         if int(batch_tiles) < 1:
@@ -316,6 +318,11 @@ class Predictor:
         self.tile, self.overlap, self.tta = int(tile), int(overlap), tta
         self.batch_tiles, self.threshold = int(batch_tiles), float(threshold)
         self.max_workspace_bytes = int(max_workspace_bytes)
+        if refine is not None:
+            from .pde import PDERefine
+            if not isinstance(refine, PDERefine):
+                raise TypeError(f"refine must be a pde.PDERefine or None, got {type(refine).__name__}")
+        self.refine = refine
 
     def plan(self, H: int, W: int) -> TilePlan:
         return tile_plan(H, W, self.tile, self.overlap, self.tta)
@@ -347,7 +354,12 @@ class Predictor:
                 # into u before the next forward all the same, so that would not matter
                 u[done:first + n].copy_(out[done - first:])
                 done = first + n
-        prob, mask = blend_tiles(u, plan, S, self.threshold)
+        if self.refine is not None:
+            from .pde import evolve
+            prob, _ = blend_tiles(u, plan, S, self.threshold, want_mask=False)
+            prob, mask = evolve(prob, self.refine, threshold=self.threshold)
+        else:
+            prob, mask = blend_tiles(u, plan, S, self.threshold)
         return prob.unsqueeze(1), mask.unsqueeze(1)
 
     def predict_batch(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

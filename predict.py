@@ -5,7 +5,8 @@ prediction on the MI355X, then an optional clean-up of the mask (drop specks, fi
     python predict.py --model m.pth --input a.png --output out --tta d4 --min-object-area 20 --fill-holes
 
 For every input image ``<stem>_mask.png`` (0 / 255, the input's own size) is written to --output, with
---save-prob also ``<stem>_prob.npy`` (float32 probabilities).
+--save-prob also ``<stem>_prob.npy`` (float32 probabilities). With ``--refine {rd,pf} --refine-steps N``
+the probabilities are evolved under the PDE before the threshold, and --save-prob saves the refined map.
 """
 import argparse
 import os
@@ -61,7 +62,10 @@ def parse_args(argv=None):
     ap.add_argument("--resize", type=_int_in(1, 32768, "a side"), nargs=2, default=None, metavar=("H", "W"),
                     help="resize every image to H x W (bilinear) before predicting and the mask back (nearest): "
                          "for models trained at one fixed size")
+    from physics_informed_image_segmentation_amd.pde import add_refine_flags, refine_from_args
+    add_refine_flags(ap)
     args = ap.parse_args(argv)
+    args.refine_preset = refine_from_args(ap, args)
     if args.overlap > args.tile // 2:
         ap.error(f"--overlap {args.overlap}: at most half the tile ({args.tile // 2}) is allowed")
     if not Path(args.model).is_file():
@@ -91,7 +95,7 @@ def main(argv=None):
     device = torch.device("cuda")
     model = load_model(Path(args.model), device)
     predictor = Predictor(model, tile=args.tile, overlap=args.overlap, tta=None if args.tta == "none" else args.tta,
-                          threshold=args.threshold)
+                          threshold=args.threshold, refine=args.refine_preset)
     out_dir = Path(args.output)
     out_dir.mkdir(parents=True, exist_ok=True)
     written = []
