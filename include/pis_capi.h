@@ -185,7 +185,7 @@ int pis_version(void);
                                       151 VGPRs); 0 in the epilogue. Step 22.25 -> 22.04 ms on one box, 22.43 ->
                                       22.39 on another (profiles/r4_t_ab_wino_out_mpf.txt, r4_u_*): 0.2-0.9 % */
 #define PIS_TUNE_WINO_F6 47 /* Winograd F(6x6,3x3) for the forward and input gradient of the deep layers whose
-                               contractions run the batched fp16x3 GEMM both ways (csrc/winograd.hip
+                               contractions run the batched fp16x3 GEMM both ways (csrc/conv3x3_plan.hip
                                wino6_layer: 64-aligned channels, neither direct nor fused, >= 10 % fewer
                                products than F(4x4) on the ragged 6 x 6 tile grid — 128^2 and 64^2 at C2;
                                their weight gradients keep F(3x3,4x4) with their own transforms): 0
@@ -194,7 +194,8 @@ int pis_version(void);
                                runtime-looped (lower-register) transforms. Measured slower on the C2 step
                                (358.7 vs 366.8 img/s, profiles/r6_f6*): the GEMMs -12 % per F(6x6)
                                launch but the 64-value transforms run at ~0.65 of F(4x4)'s bytes/s and
-                               the weight gradients' own transforms load the side stream */
+                               the weight gradients' own transforms load the side stream. Sizes
+                               the workspaces and filter operands: needs a freshly planned engine */
 #define PIS_TUNE_WGRAD_OUT 48 /* the F(3x3,4x4) weight gradient's slab sum + output transform
                                  (csrc/winograd.hip launch_wino_wgrad_out): 0 64 entries per block, one
                                  float per lane per slab row; 1 (default) float4 lanes, 64-256 entries
@@ -203,7 +204,8 @@ int pis_version(void);
                                      blocks per CU (51 KB LDS, <= 256 registers each), no register prefetch;
                                      4 (any other value) one block per CU, the next tile's loads in registers.
                                      2 vs 4: -2..-10 % per layer isolated, step 22.08 -> 21.76 ms
-                                     (profiles/r6_d1_direct_wgrad_rows.txt) */
+                                     (profiles/r6_d1_direct_wgrad_rows.txt). Sizes the weight-gradient
+                                     workspace: needs a freshly planned engine */
 #define PIS_TUNE_WINO_XFORM 50 /* the F(4x4) input transform and merged dz pass (csrc/winograd.hip
                                   wino4_input_cols_kernel / wino4_dz2_cols_kernel): 1 (default) the whole 6 x 6
                                   patch in one branch-free load phase (clamped coordinates, the border ring
@@ -400,6 +402,8 @@ int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream_t stream);
 int pis_conv3x3_dgrad_direct(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes);
 int pis_conv3x3_bwd_prep(const float* dz, int ldz, int B, int H, int W, int Cin, int Cout, void* ws_dgrad,
                          size_t ws_dgrad_bytes, void* ws_wgrad, size_t ws_wgrad_bytes, pis_stream_t stream);
+/* 0 for a shape outside pis_conv3x3_wgrad's channel contract (Cout a multiple of 64, Cin 1 or a
+ * multiple of 64): not supported, as the other size queries answer. */
 size_t pis_conv3x3_wgrad_ws(int B, int H, int W, int Cin, int Cout);
 int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw_krsc, float* db,
                       int B, int H, int W, int Cin, int Cout, int flags, void* ws, size_t ws_bytes,

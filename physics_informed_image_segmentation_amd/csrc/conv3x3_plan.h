@@ -1,0 +1,114 @@
+// The 3x3-conv planner (conv3x3_plan.hip, host only): which kernel family runs a layer's forward,
+// input gradient and weight gradient, and the workspace, kept-transform and filter-operand sizes
+// that follow. It is the only code that reads pis_tune keys to choose a 3x3-conv path; the entry
+// points (igemm.hip, wgrad.hip) ask it, per call, and launch what it says.
+#pragma once
+#include "igemm.h"
+
+namespace pis {
+
+// ---- weight-gradient detail plans (the split-K layouts of their branch) --------------------
+struct WgradPlan {
+  int bm, bn, splits, pps;
+  size_t part_bytes, bias_bytes;
+};
+// tile sizes divide the per-tap group so tiles never straddle a tap (wgrad.hip)
+WgradPlan plan_wgrad(int Mp, int Np, int P, int group_m, int group_n, int target_blocks = 2048);
+size_t wgrad_ws_bytes(const WgradPlan& pl);
+size_t colsum_ws(int64_t npix, int C);
+
+struct HaloPlan {
+  bool use;
+  int splits, seg_per_split, nseg;
+  size_t part_bytes, bias_bytes;
+};
+
+// Winograd weight gradient (csrc/winograd.hip), F(3x3, 4x4) when the 4x4 tile grid fits (pis_tune
+// key 11), else F(3x3, 2x2): V = B^T x B and E = G e G^T per tile, M_xi[n][c] = sum_tiles
+// E_xi[t][n] V_xi[t][c] as nxi = (m+2)^2 batched split-K GEMMs over the T tiles (slabs
+// [split][xi][Cout][Cin], one fixed-order reduction), dW = A^T M A; the bias gradient is a
+// channel sum of dz.
+struct WinoWgradPlan {
+  bool use, fused_bias, gemm_bias;
+  int m, nxi;
+  int64_t T;
+  WgradPlan gemm;
+  size_t off_E, off_part, off_M, off_cs, total;
+};
+
+constexpr int C1_BLOCKS = 1024;  // blocks (= partial slabs) of the Cin == 1 stream weight gradient
+
+enum WgradAlgo {
+  WGRAD_NONE = 0,   // outside pis_conv3x3_wgrad's channel contract
+  WGRAD_DIRECT,     // direct fp16x3 (direct.hip)
+  WGRAD_WINO4,      // F(3x3,4x4)
+  WGRAD_WINO2,      // F(3x3,2x2)
+  WGRAD_HALO,
+  WGRAD_C1_STREAM,  // Cin == 1, VALU stream
+  WGRAD_C1_MFMA,    // Cin == 1, padded MFMA tile
+  WGRAD_GENERIC,
+};
+
+// what pis_conv3x3_bwd_prep writes for the layer
+enum PrepKind {
+  PREP_NONE = 0,
+  PREP_DZ2,       // V(dz) for the input gradient and E for the weight gradient, one pass
+  PREP_DZ2_TMAX,  // ... with the tile maxima the fused fp16x3 input gradient reads
+  PREP_E_ONLY,    // the overlap-add input gradient (key 51) contracts the weight gradient's E
+};
+
+// one direction of the layer: the forward (C = Cin, N = Cout) or the input gradient (C = Cout, N = Cin)
+struct ConvDirPlan {
+  int C, N;            // contraction channels, outputs
+  bool direct;         // pis_tune key 29's policy takes it (given 4-aligned channel strides)
+  bool wino_wanted;    // the Winograd policy takes it without a kept transform
+  ConvAlgo wino;       // the Winograd pipeline it then runs (ALGO_NONE: the shape has none)
+  ConvAlgo wino_kept;  // ... with a kept or prepared F(4x4) transform (never F(6x6)); a kept
+                       // transform also overrides wino_wanted (resolve_conv3x3)
+  ConvAlgo fallback;   // small workspace or no policy: halo, generic, or the Cin == 1 kernels
+  size_t direct_ws, wino_ws;
+  int filter_format;   // pis_conv3x3_filter_format
+  size_t filter_bytes;
+};
+
+struct Conv3x3Plan {
+  int B, H, W, Cin, Cout;
+  ConvDirPlan fwd, dgrad;
+  bool fused_h3;      // the fused contraction runs in fp16x3 (key 22): scales after its filter planes, tile maxima
+  size_t keep_bytes;  // pis_conv3x3_keep_bytes
+  size_t ex_ws;       // pis_conv3x3_ex_ws
+  WgradAlgo wgrad;           // with 16-byte aligned operands and the workspace below
+  WgradAlgo wgrad_nodirect;  // what a misaligned operand or a small workspace demotes WGRAD_DIRECT to
+  size_t wgrad_ws, wgrad_ws_nodirect;
+  WinoWgradPlan wino_w;  // wgrad(_nodirect) == WGRAD_WINO4 / WGRAD_WINO2
+  HaloPlan halo_w;       // WGRAD_HALO
+  WgradPlan gemm_w;      // WGRAD_GENERIC, WGRAD_C1_MFMA
+  PrepKind prep;         // given 4-aligned ldz and both workspaces large enough
+};
+
+// a pure function of its arguments and the current tune state
+Conv3x3Plan plan_conv3x3(int B, int H, int W, int Cin, int Cout);
+
+// does the forward's output epilogue write the 2x2 max pool too?
+inline bool pool_fused(ConvAlgo a) {
+  return a == ALGO_DIRECT_H3 || a == ALGO_WINO6 || a == ALGO_WINO4_FUSED || a == ALGO_WINO4_GEMM;
+}
+
+// the facts only a call knows
+struct ConvCall {
+  bool is_dgrad;
+  int lds, ldd, ldm;  // channel strides of the source, the destination and (masked) the mask
+  bool masked;
+  bool has_ws;
+  size_t ws_bytes;
+  bool kept;      // a keep buffer was passed and the layer keeps a transform
+  bool prepared, filter_ready, w_unflipped;  // PIS_WINO_PREPARED, PIS_FILTER_READY, PIS_W_UNFLIPPED
+};
+// the algorithm this call launches, or ALGO_NONE with the PIS_ERR_ARG message set
+ConvAlgo resolve_conv3x3(const Conv3x3Plan& p, const ConvCall& c);
+// the weight gradient of a call that passed pis_conv3x3_wgrad's argument checks (never WGRAD_NONE),
+// or WGRAD_NONE with the message set: a direct layer that cannot run direct and whose workspace
+// is below the fallback's
+WgradAlgo resolve_wgrad(const Conv3x3Plan& p, const void* x, const void* dz, size_t ws_bytes);
+
+}  // namespace pis

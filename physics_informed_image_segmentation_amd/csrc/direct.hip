@@ -491,19 +491,6 @@ bool direct_h3_shape_ok(int H, int W, int C, int N, int ldx) {
   return H % DT_H == 0 && W % DT_W == 0 && C % DKC == 0 && N % 64 == 0 && ldx % 4 == 0 && C >= DKC;
 }
 
-bool direct_h3_wanted(int H, int W, int C, int N, int ldx) {
-  const int mode = tune_get(PIS_TUNE_DIRECT_H3);
-  if (mode == 0 || !direct_h3_shape_ok(H, W, C, N, ldx)) return false;
-  const int lo = std::min(C, N), hi = std::max(C, N);
-  if (mode == 3)  // + dec2.conv0 (256 <-> 128 at 256^2) and enc3.conv0 (128 <-> 256 at 128^2)
-    return (H >= 256 && hi <= 256) || (H >= 128 && hi <= 256 && lo <= 128);
-  if (mode == 4)  // + every <= 256-channel layer at 128^2 (enc3, dec3.conv1)
-    return H >= 128 && hi <= 256;
-  if (mode == 5)  // + every layer at 128^2 and above
-    return H >= 128;
-  return mode == 2 || (hi <= 128 && H >= 256);
-}
-
 // the direct kernel's weight splits of several layers in one launch (KRSC weights; dgrad: the
 // contraction over Cout of the ORIGINAL weights, as launch_direct_h3's dgrad_orig)
 int launch_direct_wsplit_batch(int n, const float* const* w, void* const* out, const int* Cin, const int* Cout,
@@ -1199,10 +1186,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_h3r_alt_kernel(DirectWAr
 // tile rows of the direct weight gradient: 4 (one block per CU) or 2 (pis_tune key 49: two per CU)
 static int direct_w_rows() { return tune_get(PIS_TUNE_DIRECT_W_ROWS) == 2 ? 2 : WT_H; }
 
-bool direct_w_wanted(int B, int H, int W, int Cin, int Cout, int ldx, int ldz) {
-  if (!(B > 0 && H % WT_H == 0 && W % WT_W == 0 && Cin % 64 == 0 && Cout % 64 == 0 && ldz % 4 == 0 && ldx % 4 == 0))
-    return false;
-  return direct_h3_wanted(H, W, Cin, Cout, ldx);
+bool direct_w_shape_ok(int B, int H, int W, int Cin, int Cout, int ldx, int ldz) {
+  return B > 0 && H % WT_H == 0 && W % WT_W == 0 && Cin % 64 == 0 && Cout % 64 == 0 && ldz % 4 == 0 && ldx % 4 == 0;
 }
 
 // blocks: one per CU (4-row tiles) or two (2-row tiles), split over the (Cout, Cin) 64-blocks
@@ -1223,6 +1208,7 @@ int reduce_slabs2(const float* part, int splits, int64_t n, float* dst, const fl
 
 int launch_direct_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw, float* db, int B, int H, int W,
                         int Cin, int Cout, int acc, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (!direct_w_shape_ok(B, H, W, Cin, Cout, ldx, ldz)) return set_error("direct wgrad: shape not supported"), PIS_ERR_ARG;
   if (ws_bytes < direct_w_ws_bytes(B, H, W, Cin, Cout)) return set_error("direct wgrad: workspace too small"), PIS_ERR_ARG;
   DirectWArgs g{};
   g.x = x; g.ldx = ldx; g.dz = dz; g.ldz = ldz;

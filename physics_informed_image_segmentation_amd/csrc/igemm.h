@@ -1,5 +1,6 @@
 // Implicit-GEMM argument block shared by the direct (igemm.hip) and Winograd
-// (winograd.hip) 3x3-conv paths.
+// (winograd.hip) 3x3-conv paths, and the launchers and layout helpers of those paths. Which path
+// runs is decided in conv3x3_plan.h.
 #pragma once
 #include "common.h"
 
@@ -38,19 +39,35 @@ struct IGemmArgs {
   int64_t bs_src, bs_wt, bs_dst;
 };
 
+// one value per kernel family of a 3x3 conv's forward / input gradient; conv3x3_plan.h chooses,
+// the launchers below run what they are given
+enum ConvAlgo {
+  ALGO_NONE = 0,       // no such path (a resolve error: the message is set)
+  ALGO_C1_ROW,         // Cin == 1, Cout == 64, W % 64 == 0: row kernel
+  ALGO_C1_STREAM,      // Cin == 1: stream kernel
+  ALGO_DIRECT_H3,      // direct fp16x3 (direct.hip)
+  ALGO_WINO4_FUSED,    // F(4x4,3x3), contraction fused with the output transform
+  ALGO_WINO4_GEMM,     // F(4x4,3x3) on the batched GEMM
+  ALGO_WINO4_DGRAD_T,  // ... in the overlap-add input-gradient form (pis_tune key 51)
+  ALGO_WINO6,          // F(6x6,3x3)
+  ALGO_WINO2,          // F(2x2,3x3)
+  ALGO_HALO,           // staged input halo
+  ALGO_IGEMM,          // generic implicit GEMM
+};
+
 // generic implicit GEMM (all tap modes); `batches` independent problems via gridDim.y
 int launch_igemm(const IGemmArgs& a, hipStream_t s, int batches = 1);
-// 3x3 conv (fwd or dgrad-on-flipped-weights): halo kernel when the grid allows, else igemm
-int launch_conv3x3(const IGemmArgs& a, hipStream_t s);
-// Winograd F(4x4,3x3) / F(2x2,3x3) path of the same conv (winograd.hip); B = images in a.src
-bool wino_ok(const IGemmArgs& a);
-// output tile edge of the Winograd fwd/dgrad path for this grid: 4 (F(4x4,3x3)) or 2
-int wino_tile(int H, int W);
-size_t wino_ws_bytes(int B, int H, int W, int C, int N);
+// 3x3 conv (fwd or dgrad-on-flipped-weights) from a staged input halo (W % 16 == 0, H % 8 == 0,
+// 4-aligned Csrc and lds)
+int launch_conv3x3_halo(const IGemmArgs& a, hipStream_t s);
+// the Winograd pipelines of the same conv (winograd.hip; algo: one of the ALGO_WINO*); B = images in a.src
+// workspace of the F(m x m, 3x3) pipelines, m = 4 or 2, and of F(6x6,3x3)
+size_t wino_ws_bytes(int m, int B, int H, int W, int C, int N);
+size_t wino6_ws_bytes(int B, int H, int W, int C, int N);
 // keep_v (optional, F(4x4) only): V is written there instead of the workspace and left for
 // the layer's weight gradient (pis_conv3x3_wgrad_keep)
 // v_ready: V (F(4x4) only) is already in the workspace (pis_conv3x3_bwd_prep)
-int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v = nullptr,
+int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v = nullptr,
                    bool v_ready = false);
 float* wino_v_slot(void* ws, int C, int N);
 // one pass over dz: V (input-gradient input transform) and E + bias partials (weight gradient)
@@ -58,14 +75,10 @@ float* wino_v_slot(void* ws, int C, int N);
 int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float* V, float* E, float* bpart,
                     hipStream_t s, float* tmax = nullptr);
 float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N);
-bool wino_fused_h3_planned(int B, int H, int W, int C, int N);
 // pis_conv3x3_bwd_prep's record of the V it wrote into ws (checked by the prepared dgrad); e != NULL:
 // the overlap-add form (pis_tune key 51) — no V, the input gradient contracts the weight
 // gradient's E at e (C = Cout contraction channels, N = Cin)
 void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax, const float* e = nullptr);
-bool wino_dgrad_t_planned(int B, int H, int W, int C, int N);
-// does pis_conv3x3_dgrad_ex take F(4x4,3x3) Winograd for this layer with this workspace?
-bool dgrad_wino4_planned(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes);
 // Winograd weight-gradient pieces for tile edge m (2: F(3x3,2x2), 4: F(3x3,4x4)), nxi = (m+2)^2:
 // V[nxi][T][C] of x, E[nxi][T][N] of dz, dW from M[nxi][N][C]
 int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float* V, hipStream_t s, int m);
@@ -74,9 +87,12 @@ int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float
 int launch_wino_dz(const float* dz, int ldz, int B, int H, int W, int N, float* E, hipStream_t s, int m,
                    float* bpart = nullptr);
 int wino_dz_blocks(int B, int H, int W, int N, int m);
-// F(6x6,3x3) for the forward and input gradient of this layer (pis_tune key 47; symmetric in Cin / Cout)
-bool wino6_layer(int B, int H, int W, int Cin, int Cout);
+// the filter operands computed ahead (pis_conv3x3_filter(s)): C contraction channels, N outputs;
+// format as pis_conv3x3_filter_format
 int launch_wino6_filter_only(const float* w, int C, int N, int dgrad, void* out, hipStream_t s);
+int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s);
+int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, const int* C, const int* N,
+                              const int* dgrad, const int* format, hipStream_t s);
 int wino_dz_blocks_max(int B, int H, int W, int N, int m);  // the largest grid a dz pass of F(m x m) launches (rows of bias partials)
 // M: nsplit split-K slabs sstride floats apart, summed in slab order (nsplit > 1 needs m == 4)
 // The F(3x3,4x4) weight gradient's bias gradient, folded into its output-transform launch:
@@ -94,18 +110,17 @@ constexpr float WINO4_BIAS_SCALE = (float)(1.0 / ((double)(1.0f / 3.0f) * (doubl
 int launch_wino_wgrad_out(const float* M, int N, int C, float* dw, int accumulate, hipStream_t s, int m,
                           int nsplit = 1, int64_t sstride = 0, WgradOutBias bias = WgradOutBias{});
 
-// direct 3x3 conv in fp16x3 (direct.hip): shapes it covers, its workspace (split weights), the
-// launch (dgrad_orig: an input gradient whose a.wt holds the ORIGINAL KRSC weights)
+// direct 3x3 conv in fp16x3 (direct.hip): shapes it covers (a contraction of C channels into N
+// outputs; the layer's weight gradient), its workspace (split weights), the launch (dgrad_orig: an
+// input gradient whose a.wt holds the ORIGINAL KRSC weights)
 bool direct_h3_shape_ok(int H, int W, int C, int N, int ldx);
+bool direct_w_shape_ok(int B, int H, int W, int Cin, int Cout, int ldx, int ldz);
 size_t direct_h3_ws_bytes(int C, int N);
 int launch_direct_h3(const IGemmArgs& a, int B, void* ws, size_t ws_bytes, hipStream_t s, bool dgrad_orig,
                      bool ready = false);
 int launch_direct_wsplit_batch(int n, const float* const* w, void* const* out, const int* Cin, const int* Cout,
                                const int* dgrad, hipStream_t s);
-// pis_tune key 29's policy for a contraction of C channels into N outputs on an H x W grid
-bool direct_h3_wanted(int H, int W, int C, int N, int ldx);
-// ... and for the layer's weight gradient (the direct fp16x3 wgrad kernel): its workspace, launch
-bool direct_w_wanted(int B, int H, int W, int Cin, int Cout, int ldx, int ldz);
+// the layer's weight gradient (the direct fp16x3 wgrad kernel): its workspace, launch
 size_t direct_w_ws_bytes(int B, int H, int W, int Cin, int Cout);
 int launch_direct_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw, float* db, int B, int H, int W,
                         int Cin, int Cout, int acc, void* ws, size_t ws_bytes, hipStream_t s);

@@ -12,7 +12,7 @@
 // 16-byte rows: lane (i, h) of a wave supplies A[i][k] for k = 8g + 4h + t,
 // t = 0..3, i.e. one ds_read_b128 feeds four MFMAs (the k-permutation is
 // applied identically to A and Bt, so the sum is unchanged).
-#include "igemm.h"
+#include "conv3x3_plan.h"
 
 namespace pis {
 
@@ -366,11 +366,6 @@ __global__ __launch_bounds__(256, (BN >= 256 ? 2 : 1)) void conv3x3_halo_kernel(
   }
 }
 
-static bool halo_ok(const IGemmArgs& a) {
-  return a.tap_mode == TAP_CONV3 && a.epi == EPI_NHWC && a.W % 16 == 0 && a.H % 8 == 0 &&
-         a.Csrc % 4 == 0 && a.lds % 4 == 0 && a.ldw % 4 == 0;
-}
-
 
 int launch_igemm(const IGemmArgs& a, hipStream_t s, int batches) {
   // tile choice: BN=64 for narrow outputs, BM=128; K-step from the tuning table
@@ -399,8 +394,9 @@ int launch_igemm(const IGemmArgs& a, hipStream_t s, int batches) {
   return launch_status("igemm_f32");
 }
 
-int launch_conv3x3(const IGemmArgs& a, hipStream_t s) {
-  if (!halo_ok(a) || !tune_get(PIS_TUNE_CONV_HALO)) return launch_igemm(a, s);
+int launch_conv3x3_halo(const IGemmArgs& a, hipStream_t s) {
+  if (a.tap_mode != TAP_CONV3 || a.epi != EPI_NHWC || a.W % 16 || a.H % 8 || a.Csrc % 4 || a.lds % 4 || a.ldw % 4)
+    return set_error("conv3x3_halo: needs W % 16 == 0, H % 8 == 0 and 4-aligned channels"), PIS_ERR_ARG;
   if (tune_get(PIS_TUNE_DEBUG_NOLOAD)) const_cast<IGemmArgs&>(a).flags |= PIS_DEBUG_NOLOAD;
   const int tiles = (a.M / (8 * 16));
   const int variant = tune_get(PIS_TUNE_HALO_VARIANT);
@@ -557,81 +553,87 @@ __global__ void convt_prep_kernel(const float* __restrict__ w, float* __restrict
 
 using namespace pis;
 
-// Winograd policy (winograd.hip): where its GEMMs stay MFMA-bound and beat the direct kernels
-static bool wino_wanted_dims(int H, int W, int C, int N) {
-  const int mode = tune_get(PIS_TUNE_WINOGRAD);
-  if (mode == 0 || H % 2 || W % 2 || C % 4 || N % 4) return false;
-  if (mode == 2) return true;
-  // measured (tools/bench_kernels.py --key 8 --variants 1,2 --ops fwd,dgrad, B=8):
-  // F(4x4,3x3) beats the direct halo kernels from 128 channels on either side (dec1.conv0
-  // fwd -22 %, dgrad -27 %; enc2.conv1 -41 %) and only loses at 64 -> 64 (+1.5-3 %);
-  // F(2x2,3x3) needs >= 256 contraction channels and 128 outputs. With the bf16x6 GEMMs
-  // (key 10 = 3) F(4x4,3x3) also wins at 64 -> 64 (enc1.conv1 fwd -13 %, dgrad -11 %).
-  if (wino_tile(H, W) == 4)
-    return C >= 128 || N >= 128 || (tune_get(PIS_TUNE_WINO_TILE) >= 3 && C >= 64 && N >= 64);
-  return C >= 256 && N >= 128;
+// the IGemmArgs of a 3x3 conv over an H x W grid: C source channels into N outputs (forward:
+// Cin into Cout from the KRSC weights; input gradient: Cout into Cin); the caller adds its epilogue
+// operands
+static IGemmArgs conv3x3_args(const float* src, int lds, const float* wt, int C, int N, float* dst, int ldd, int B,
+                              int H, int W, int flags) {
+  IGemmArgs a{};
+  a.src = src; a.lds = lds; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.M = B * H * W;
+  a.Csrc = C; a.ntaps = 9; a.tap_mode = TAP_CONV3; a.wt = wt; a.ldw = 9 * C; a.N = N;
+  a.epi = EPI_NHWC; a.dst = dst; a.ldd = ldd;
+  a.flags = flags & (PIS_RELU | PIS_SCALE | PIS_MASK | PIS_ACCUMULATE);
+  a.w_unflipped = (flags & PIS_W_UNFLIPPED) != 0;
+  a.filter_ready = (flags & PIS_FILTER_READY) != 0;
+  return a;
 }
 
-namespace pis {
-bool wino_fused_wanted(int B, int H, int W, int C, int N);  // winograd.hip
+static ConvAlgo resolve(const Conv3x3Plan& p, const IGemmArgs& a, const void* ws, size_t ws_bytes, bool kept,
+                        bool prepared) {
+  return resolve_conv3x3(p, ConvCall{a.is_dgrad != 0, a.lds, a.ldd, a.ldm, (a.flags & PIS_MASK) != 0, ws != nullptr,
+                                     ws_bytes, kept, prepared, a.filter_ready != 0, a.w_unflipped != 0});
 }
 
-// F(6x6,3x3) for a layer's forward and input gradient (pis_tune key 47; csrc/winograd.hip
-// launch_wino6): both directions on the batched fp16x3 GEMM (Winograd-wanted, neither direct nor
-// fused), 64-aligned channels, an F(4x4)-capable grid (the weight gradient keeps F(3x3,4x4)), and
-// at least 10 % fewer products on the ragged 6 x 6 tile grid: 128^2 and 64^2 at C2 (0.84 of
-// F(4x4)'s), not 32^2 (ceil(32 / 6)^2 x 64 = 32^2 / 16 x 36: no gain)
-bool pis::wino6_layer(int B, int H, int W, int Cin, int Cout) {
-  if (tune_get(PIS_TUNE_WINO_F6) == 0 || tune_get(PIS_TUNE_WINO_TILE) != 4 || B <= 0) return false;
-  if (wino_tile(H, W) != 4 || Cin % 64 || Cout % 64) return false;
-  if (direct_h3_wanted(H, W, Cin, Cout, 4) || direct_h3_wanted(H, W, Cout, Cin, 4)) return false;
-  if (!wino_wanted_dims(H, W, Cin, Cout) || !wino_wanted_dims(H, W, Cout, Cin)) return false;
-  if (wino_fused_wanted(B, H, W, Cin, Cout) || wino_fused_wanted(B, H, W, Cout, Cin)) return false;
-  const int64_t p6 = (int64_t)64 * ((H + 5) / 6) * ((W + 5) / 6), p4 = (int64_t)36 * (H / 4) * (W / 4);
-  return 10 * p6 <= 9 * p4;
-}
-
-static int dispatch_conv3x3(const IGemmArgs& a, int B, void* ws, size_t ws_bytes, hipStream_t s,
-                            float* keep_v = nullptr, bool v_ready = false) {
-  // the direct fp16x3 kernel (pis_tune key 29) where its policy takes the layer; a kept forward
-  // transform is then still owed to the layer's Winograd weight gradient
-  // (PIS_FILTER_READY here: a.wt is the layer's split from pis_conv3x3_filter(s), format 3)
-  if (ws && !v_ready && a.tap_mode == TAP_CONV3 && a.epi == EPI_NHWC &&
-      direct_h3_wanted(a.H, a.W, a.Csrc, a.N, a.lds) &&
-      (a.filter_ready || ws_bytes >= direct_h3_ws_bytes(a.Csrc, a.N))) {
-    int rc = launch_direct_h3(a, B, ws, ws_bytes, s, a.w_unflipped != 0, a.filter_ready);
-    if (!rc && keep_v) rc = launch_wino_input(a.src, a.lds, B, a.H, a.W, a.Csrc, keep_v, s, 4);
-    return rc;
+// run the resolved algorithm; keep_v: the layer's kept F(4x4) input transform, which the paths
+// that do not compute it still owe to the weight gradient
+static int launch_conv3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, size_t ws_bytes, hipStream_t s,
+                          float* keep_v = nullptr, bool v_ready = false) {
+  int rc = PIS_ERR_ARG;
+  switch (algo) {
+    case ALGO_NONE: return PIS_ERR_ARG;
+    case ALGO_C1_ROW:
+      if (a.H % 4 == 0)
+        hipLaunchKernelGGL(conv3x3_c1_row_kernel<4>, dim3((unsigned)(B * (a.H / 4) * (a.W / 64))), dim3(256), 0, s, a.src,
+                           a.lds, a.wt, a.bias, a.scale, a.dst, a.ldd, a.H, a.W, a.flags);
+      else
+        hipLaunchKernelGGL(conv3x3_c1_row_kernel<1>, dim3((unsigned)(B * a.H * (a.W / 64))), dim3(256), 0, s, a.src,
+                           a.lds, a.wt, a.bias, a.scale, a.dst, a.ldd, a.H, a.W, a.flags);
+      return launch_status("conv3x3_c1_row");
+    case ALGO_C1_STREAM: {
+      PIS_CHECK_ARG(a.N <= 1024, "pis_conv3x3_fwd: Cin==1 path supports Cout<=1024");
+      const int64_t threads = (int64_t)B * a.H * a.W * (a.N / 4);
+      const int64_t blocks = std::min<int64_t>(cdiv(threads, 256), 4096);
+      hipLaunchKernelGGL(conv3x3_c1_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.src, a.lds, a.wt, a.bias,
+                         a.scale, a.dst, a.ldd, B, a.H, a.W, a.N, a.flags);
+      return launch_status("conv3x3_c1_fwd");
+    }
+    case ALGO_WINO4_FUSED:
+    case ALGO_WINO4_GEMM:
+    case ALGO_WINO4_DGRAD_T:
+    case ALGO_WINO6:
+    case ALGO_WINO2: return launch_wino3x3(algo, a, B, ws, s, keep_v, v_ready);
+    // (PIS_FILTER_READY here: a.wt is the layer's split from pis_conv3x3_filter(s), format 3)
+    case ALGO_DIRECT_H3: rc = launch_direct_h3(a, B, ws, ws_bytes, s, a.w_unflipped != 0, a.filter_ready); break;
+    case ALGO_HALO: rc = launch_conv3x3_halo(a, s); break;
+    case ALGO_IGEMM: rc = launch_igemm(a, s); break;
   }
-  // a kept transform is computed either way: then Winograd wins even where the plain policy
-  // prefers the direct kernel (64 -> 64 at 512^2: +2 % forward, -27 % weight gradient)
-  if (ws && wino_ok(a) && (keep_v || wino_wanted_dims(a.H, a.W, a.Csrc, a.N)) &&
-      ws_bytes >= wino_ws_bytes(B, a.H, a.W, a.Csrc, a.N))
-    return launch_wino3x3(a, B, ws, s, keep_v, v_ready);
-  if (a.filter_ready) {
-    set_error("conv3x3: PIS_FILTER_READY but this call does not take the F(4x4,3x3) path");
-    return PIS_ERR_ARG;
-  }
-  if (v_ready) {
-    set_error("pis_conv3x3_dgrad_ex: PIS_WINO_PREPARED but this call does not take the Winograd path");
-    return PIS_ERR_ARG;
-  }
-  int rc = launch_conv3x3(a, s);
-  // direct path taken (e.g. a small workspace): the kept transform is still owed to the wgrad
   if (!rc && keep_v) rc = launch_wino_input(a.src, a.lds, B, a.H, a.W, a.Csrc, keep_v, s, 4);
   return rc;
 }
 
-size_t wino_wgrad_keep_bytes(int B, int H, int W, int Cin, int Cout);  // wgrad.hip
-
 extern "C" size_t pis_conv3x3_ex_ws(int B, int H, int W, int Cin, int Cout) {
-  size_t need = 0;
-  if (direct_h3_wanted(H, W, Cin, Cout, 4)) need = std::max(need, direct_h3_ws_bytes(Cin, Cout));
-  if (direct_h3_wanted(H, W, Cout, Cin, 4)) need = std::max(need, direct_h3_ws_bytes(Cout, Cin));
-  const bool keepable = Cin % 4 == 0 && wino_tile(H, W) == 4 && wino_wgrad_keep_bytes(B, H, W, Cin, Cout) > 0;
-  if (keepable || wino_wanted_dims(H, W, Cin, Cout)) need = std::max(need, wino_ws_bytes(B, H, W, Cin, Cout));  // fwd
-  if (wino_wanted_dims(H, W, Cout, Cin)) need = std::max(need, wino_ws_bytes(B, H, W, Cout, Cin));  // dgrad
-  return need;
+  return plan_conv3x3(B, H, W, Cin, Cout).ex_ws;
+}
+
+extern "C" size_t pis_conv3x3_keep_bytes(int B, int H, int W, int Cin, int Cout) {
+  return plan_conv3x3(B, H, W, Cin, Cout).keep_bytes;
+}
+
+extern "C" size_t pis_conv3x3_filter_bytes(int B, int H, int W, int Cin, int Cout, int dgrad) {
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  return (dgrad ? p.dgrad : p.fwd).filter_bytes;
+}
+
+extern "C" int pis_conv3x3_filter_format(int B, int H, int W, int Cin, int Cout, int dgrad) {
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  return (dgrad ? p.dgrad : p.fwd).filter_format;
+}
+
+// does pis_conv3x3_dgrad_ex take the direct fp16x3 kernel (which reads the original weights
+// with PIS_W_UNFLIPPED, no flipped copy)?
+extern "C" int pis_conv3x3_dgrad_direct(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes) {
+  const ConvDirPlan d = plan_conv3x3(B, H, W, Cin, Cout).dgrad;
+  return B > 0 && d.direct && ldz % 4 == 0 && ws_bytes >= d.direct_ws;
 }
 
 extern "C" int pis_conv3x3_fwd(const float* x, int ldx, const float* w_krsc, const float* bias,
@@ -640,29 +642,36 @@ extern "C" int pis_conv3x3_fwd(const float* x, int ldx, const float* w_krsc, con
   return pis_conv3x3_fwd_ex(x, ldx, w_krsc, bias, scale, y, ldy, B, H, W, Cin, Cout, flags, nullptr, 0, stream);
 }
 
-extern "C" size_t pis_conv3x3_keep_bytes(int B, int H, int W, int Cin, int Cout) {
-  if (Cin % 4 || wino_tile(H, W) != 4 || tune_get(PIS_TUNE_WINOGRAD) == 0) return 0;
-  if (wino6_layer(B, H, W, Cin, Cout)) return 0;  // F(6x6) forward: the weight gradient transforms x itself
-  return wino_wgrad_keep_bytes(B, H, W, Cin, Cout);
+extern "C" int pis_conv3x3_fwd_ex(const float* x, int ldx, const float* w_krsc, const float* bias,
+                                  const float* scale, float* y, int ldy, int B, int H, int W, int Cin,
+                                  int Cout, int flags, void* ws, size_t ws_bytes, pis_stream_t stream) {
+  PIS_CHECK_ARG(x && w_krsc && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
+                "pis_conv3x3_fwd: bad arguments");
+  PIS_CHECK_ARG(!(flags & PIS_SCALE) || scale, "pis_conv3x3_fwd: PIS_SCALE without scale");
+  PIS_CHECK_ARG(ldy % 4 == 0 && Cout % 4 == 0, "pis_conv3x3_fwd: ldy/Cout must be multiples of 4");
+  PIS_CHECK_ARG(!(flags & PIS_FILTER_READY) || Cin > 1, "pis_conv3x3_fwd: PIS_FILTER_READY with Cin == 1");
+  PIS_CHECK_ARG(Cin == 1 || (Cin % 4 == 0 && ldx % 4 == 0), "pis_conv3x3_fwd: Cin/ldx must be multiples of 4");
+  IGemmArgs a = conv3x3_args(x, ldx, w_krsc, Cin, Cout, y, ldy, B, H, W, flags & (PIS_RELU | PIS_SCALE | PIS_ACCUMULATE |
+                                                                                 PIS_FILTER_READY));
+  a.bias = bias; a.scale = scale;
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  return launch_conv3x3(resolve(p, a, ws, ws_bytes, false, false), a, B, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pis_conv3x3_fwd_keep(const float* x, int ldx, const float* w_krsc, const float* bias,
                                     const float* scale, float* y, int ldy, int B, int H, int W, int Cin,
                                     int Cout, int flags, void* ws, size_t ws_bytes, float* keep,
                                     pis_stream_t stream) {
-  const size_t kb = pis_conv3x3_keep_bytes(B, H, W, Cin, Cout);
-  if (!keep || kb == 0)
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  if (!keep || p.keep_bytes == 0)
     return pis_conv3x3_fwd_ex(x, ldx, w_krsc, bias, scale, y, ldy, B, H, W, Cin, Cout, flags, ws, ws_bytes, stream);
   PIS_CHECK_ARG(x && w_krsc && y && B > 0 && ldx % 4 == 0 && ldy % 4 == 0 && Cout % 4 == 0,
                 "pis_conv3x3_fwd_keep: bad arguments");
   PIS_CHECK_ARG(!(flags & PIS_SCALE) || scale, "pis_conv3x3_fwd_keep: PIS_SCALE without scale");
-  IGemmArgs a{};
-  a.src = x; a.lds = ldx; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.M = B * H * W;
-  a.Csrc = Cin; a.ntaps = 9; a.tap_mode = TAP_CONV3; a.wt = w_krsc; a.ldw = 9 * Cin; a.N = Cout;
-  a.epi = EPI_NHWC; a.bias = bias; a.scale = scale; a.dst = y; a.ldd = ldy;
-  a.flags = flags & (PIS_RELU | PIS_SCALE | PIS_ACCUMULATE);
-  a.filter_ready = (flags & PIS_FILTER_READY) != 0;
-  return dispatch_conv3x3(a, B, ws, ws_bytes, (hipStream_t)stream, keep);
+  IGemmArgs a = conv3x3_args(x, ldx, w_krsc, Cin, Cout, y, ldy, B, H, W, flags & (PIS_RELU | PIS_SCALE | PIS_ACCUMULATE |
+                                                                                 PIS_FILTER_READY));
+  a.bias = bias; a.scale = scale;
+  return launch_conv3x3(resolve(p, a, ws, ws_bytes, true, false), a, B, ws, ws_bytes, (hipStream_t)stream, keep);
 }
 
 extern "C" int pis_conv3x3_fwd_pool(const float* x, int ldx, const float* w_krsc, const float* bias,
@@ -675,65 +684,21 @@ extern "C" int pis_conv3x3_fwd_pool(const float* x, int ldx, const float* w_krsc
                     Cout % 4 == 0,
                 "pis_conv3x3_fwd_pool: bad arguments");
   PIS_CHECK_ARG(!(flags & PIS_SCALE) || scale, "pis_conv3x3_fwd_pool: PIS_SCALE without scale");
-  const bool kept = keep && pis_conv3x3_keep_bytes(B, H, W, Cin, Cout) > 0;
-  IGemmArgs a{};
-  a.src = x; a.lds = ldx; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.M = B * H * W;
-  a.Csrc = Cin; a.ntaps = 9; a.tap_mode = TAP_CONV3; a.wt = w_krsc; a.ldw = 9 * Cin; a.N = Cout;
-  a.epi = EPI_NHWC; a.bias = bias; a.scale = scale; a.dst = y; a.ldd = ldy;
-  a.flags = flags & (PIS_RELU | PIS_SCALE);
-  a.filter_ready = (flags & PIS_FILTER_READY) != 0;
-  // the direct fp16x3 kernel and the F(4x4,3x3) output epilogues pool the tile they just wrote;
-  // every other path pools after
-  if (Cin > 1 && ws && direct_h3_wanted(H, W, Cin, Cout, ldx) &&
-      (a.filter_ready || ws_bytes >= direct_h3_ws_bytes(Cin, Cout))) {
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  float* keep_v = p.keep_bytes > 0 ? keep : nullptr;
+  IGemmArgs a = conv3x3_args(x, ldx, w_krsc, Cin, Cout, y, ldy, B, H, W, flags & (PIS_RELU | PIS_SCALE | PIS_FILTER_READY));
+  a.bias = bias; a.scale = scale;
+  // the direct fp16x3 kernel and the F(4x4,3x3) / F(6x6,3x3) output epilogues pool the tile they
+  // just wrote; every other path pools after
+  const ConvAlgo algo = resolve(p, a, ws, ws_bytes, keep_v != nullptr, false);
+  if (pool_fused(algo)) {
     a.pool = pool;
-    return dispatch_conv3x3(a, B, ws, ws_bytes, (hipStream_t)stream, kept ? keep : nullptr);
-  }
-  if (Cin > 1 && ws && wino_ok(a) && wino_tile(H, W) == 4 && (kept || wino_wanted_dims(H, W, Cin, Cout)) &&
-      ws_bytes >= wino_ws_bytes(B, H, W, Cin, Cout)) {
-    a.pool = pool;
-    return dispatch_conv3x3(a, B, ws, ws_bytes, (hipStream_t)stream, kept ? keep : nullptr);
+    return launch_conv3x3(algo, a, B, ws, ws_bytes, (hipStream_t)stream, keep_v);
   }
   int rc = pis_conv3x3_fwd_keep(x, ldx, w_krsc, bias, scale, y, ldy, B, H, W, Cin, Cout, flags, ws, ws_bytes,
                                 keep, stream);
   if (rc) return rc;
   return pis_maxpool2x2_fwd(y, ldy, pool, B, H, W, Cout, stream);
-}
-
-extern "C" int pis_conv3x3_fwd_ex(const float* x, int ldx, const float* w_krsc, const float* bias,
-                                  const float* scale, float* y, int ldy, int B, int H, int W, int Cin,
-                                  int Cout, int flags, void* ws, size_t ws_bytes, pis_stream_t stream) {
-  PIS_CHECK_ARG(x && w_krsc && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
-                "pis_conv3x3_fwd: bad arguments");
-  PIS_CHECK_ARG(!(flags & PIS_SCALE) || scale, "pis_conv3x3_fwd: PIS_SCALE without scale");
-  PIS_CHECK_ARG(ldy % 4 == 0 && Cout % 4 == 0, "pis_conv3x3_fwd: ldy/Cout must be multiples of 4");
-  hipStream_t s = (hipStream_t)stream;
-  PIS_CHECK_ARG(!(flags & PIS_FILTER_READY) || Cin > 1, "pis_conv3x3_fwd: PIS_FILTER_READY with Cin == 1");
-  if (Cin == 1 && Cout == 64 && W % 64 == 0) {
-    if (H % 4 == 0)
-      hipLaunchKernelGGL(conv3x3_c1_row_kernel<4>, dim3((unsigned)(B * (H / 4) * (W / 64))), dim3(256), 0, s, x, ldx,
-                         w_krsc, bias, scale, y, ldy, H, W, flags);
-    else
-      hipLaunchKernelGGL(conv3x3_c1_row_kernel<1>, dim3((unsigned)(B * H * (W / 64))), dim3(256), 0, s, x, ldx,
-                         w_krsc, bias, scale, y, ldy, H, W, flags);
-    return launch_status("conv3x3_c1_row");
-  }
-  if (Cin == 1) {
-    PIS_CHECK_ARG(Cout <= 1024, "pis_conv3x3_fwd: Cin==1 path supports Cout<=1024");
-    const int64_t threads = (int64_t)B * H * W * (Cout / 4);
-    const int64_t blocks = std::min<int64_t>(cdiv(threads, 256), 4096);
-    hipLaunchKernelGGL(conv3x3_c1_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, w_krsc, bias,
-                       scale, y, ldy, B, H, W, Cout, flags);
-    return launch_status("conv3x3_c1_fwd");
-  }
-  PIS_CHECK_ARG(Cin % 4 == 0 && ldx % 4 == 0, "pis_conv3x3_fwd: Cin/ldx must be multiples of 4");
-  IGemmArgs a{};
-  a.src = x; a.lds = ldx; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.M = B * H * W;
-  a.Csrc = Cin; a.ntaps = 9; a.tap_mode = TAP_CONV3; a.wt = w_krsc; a.ldw = 9 * Cin; a.N = Cout;
-  a.epi = EPI_NHWC; a.bias = bias; a.scale = scale; a.dst = y; a.ldd = ldy;
-  a.flags = flags & (PIS_RELU | PIS_SCALE | PIS_ACCUMULATE);
-  a.filter_ready = (flags & PIS_FILTER_READY) != 0;
-  return dispatch_conv3x3(a, B, ws, ws_bytes, s);
 }
 
 extern "C" int pis_conv3x3_flip(const float* w_krsc, float* w_flip, int Cin, int Cout,
@@ -746,61 +711,18 @@ extern "C" int pis_conv3x3_flip(const float* w_krsc, float* w_flip, int Cin, int
   return launch_status("conv3x3_flip");
 }
 
-namespace pis {  // winograd.hip
-int wino_filter_format(int B, int H, int W, int C, int N, bool kept);
-int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s);
-int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, const int* C, const int* N,
-                              const int* dgrad, const int* format, hipStream_t s);
-}  // namespace pis
-
-// the filter transform pis_conv3x3_{fwd_keep,fwd_pool,dgrad_ex} would compute (engine shapes:
-// kept forward transforms, prepared 32-aligned input gradients)
-static int filter_format(int B, int H, int W, int Cin, int Cout, int dgrad) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cin % 4 || Cout % 4 || Cin < 4) return 0;
-  // 4: the F(6x6,3x3) transform U[64][N][C] (input gradient: from the ORIGINAL weights)
-  if (wino6_layer(B, H, W, Cin, Cout)) return 4;
-  // 3: the call takes the direct fp16x3 kernel — its "filter transform" is the weight split
-  if (dgrad ? direct_h3_wanted(H, W, Cout, Cin, 4) : direct_h3_wanted(H, W, Cin, Cout, 4)) return 3;
-  if (dgrad) {
-    if (Cin % 32 || Cout % 32 || !wino_wanted_dims(H, W, Cout, Cin)) return 0;
-    return wino_filter_format(B, H, W, Cout, Cin, false);
-  }
-  if (pis_conv3x3_keep_bytes(B, H, W, Cin, Cout) == 0 && !wino_wanted_dims(H, W, Cin, Cout)) return 0;
-  return wino_filter_format(B, H, W, Cin, Cout, pis_conv3x3_keep_bytes(B, H, W, Cin, Cout) > 0);
-}
-
-extern "C" size_t pis_conv3x3_filter_bytes(int B, int H, int W, int Cin, int Cout, int dgrad) {
-  const int f = filter_format(B, H, W, Cin, Cout, dgrad);
-  if (f == 0) return 0;
-  const size_t nc = (size_t)36 * Cin * Cout;
-  const int C = dgrad ? Cout : Cin, N = dgrad ? Cin : Cout;  // contraction, outputs
-  if (f == 3) return direct_h3_ws_bytes(C, N);
-  if (f == 4) return (size_t)64 * Cin * Cout * sizeof(float);
-  if (f == 2 && tune_get(PIS_TUNE_WINO_GEMM_OUT_H3) != 0)  // fp16x3: hi / lo planes + one scale per output
-    return 2 * nc * sizeof(_Float16) + (size_t)N * sizeof(float);
-  return f == 2 ? 3 * nc * sizeof(__bf16) : nc * sizeof(float);
-}
-
 extern "C" int pis_conv3x3_filter(const float* w, int B, int H, int W, int Cin, int Cout, int dgrad, void* out,
                                   size_t out_bytes, pis_stream_t stream) {
-  const int f = filter_format(B, H, W, Cin, Cout, dgrad);
-  PIS_CHECK_ARG(w && out && f != 0, "pis_conv3x3_filter: no F(4x4,3x3) GEMM path for these shapes");
-  PIS_CHECK_ARG(out_bytes >= pis_conv3x3_filter_bytes(B, H, W, Cin, Cout, dgrad), "pis_conv3x3_filter: output too small");
-  if (f == 3) {  // the direct kernel's split (input gradient: of the ORIGINAL weights)
-    const int dg = dgrad ? 1 : 0;
-    void* o = out;
-    return launch_direct_wsplit_batch(1, &w, &o, &Cin, &Cout, &dg, (hipStream_t)stream);
-  }
-  // forward: contraction C = Cin, outputs N = Cout; input gradient: C = Cout, N = Cin
-  if (f == 4)
-    return dgrad ? launch_wino6_filter_only(w, Cout, Cin, 1, out, (hipStream_t)stream)
-                 : launch_wino6_filter_only(w, Cin, Cout, 0, out, (hipStream_t)stream);
-  return dgrad ? launch_wino4_filter_only(w, Cout, Cin, 1, f, out, (hipStream_t)stream)
-               : launch_wino4_filter_only(w, Cin, Cout, 0, f, out, (hipStream_t)stream);
-}
-
-extern "C" int pis_conv3x3_filter_format(int B, int H, int W, int Cin, int Cout, int dgrad) {
-  return filter_format(B, H, W, Cin, Cout, dgrad);
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  const ConvDirPlan& d = dgrad ? p.dgrad : p.fwd;
+  PIS_CHECK_ARG(w && out && d.filter_format != 0, "pis_conv3x3_filter: no F(4x4,3x3) GEMM path for these shapes");
+  PIS_CHECK_ARG(out_bytes >= d.filter_bytes, "pis_conv3x3_filter: output too small");
+  const int dg = dgrad ? 1 : 0;
+  if (d.filter_format == 3)  // the direct kernel's split (input gradient: of the ORIGINAL weights)
+    return launch_direct_wsplit_batch(1, &w, &out, &Cin, &Cout, &dg, (hipStream_t)stream);
+  // d.C contraction channels into d.N outputs
+  if (d.filter_format == 4) return launch_wino6_filter_only(w, d.C, d.N, dg, out, (hipStream_t)stream);
+  return launch_wino4_filter_only(w, d.C, d.N, dg, d.filter_format, out, (hipStream_t)stream);
 }
 
 extern "C" int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream_t stream) {
@@ -815,19 +737,19 @@ extern "C" int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream
   int nw = 0, nd = 0;
   for (int k = 0; k < n; ++k) {
     const pis_filter_job& j = jobs[k];
-    const int f = filter_format(j.B, j.H, j.W, j.Cin, j.Cout, j.dgrad);
-    PIS_CHECK_ARG(j.w && j.out && f != 0, "pis_conv3x3_filters: a job has no filter transform (no F(4x4,3x3) GEMM "
-                                          "or direct path)");
-    PIS_CHECK_ARG(j.out_bytes >= pis_conv3x3_filter_bytes(j.B, j.H, j.W, j.Cin, j.Cout, j.dgrad),
-                  "pis_conv3x3_filters: a job's output is too small");
-    if (f == 3) {
+    const Conv3x3Plan p = plan_conv3x3(j.B, j.H, j.W, j.Cin, j.Cout);
+    const ConvDirPlan& d = j.dgrad ? p.dgrad : p.fwd;
+    PIS_CHECK_ARG(j.w && j.out && d.filter_format != 0, "pis_conv3x3_filters: a job has no filter transform (no "
+                                                        "F(4x4,3x3) GEMM or direct path)");
+    PIS_CHECK_ARG(j.out_bytes >= d.filter_bytes, "pis_conv3x3_filters: a job's output is too small");
+    if (d.filter_format == 3) {
       dw[nd] = j.w; dout[nd] = j.out; dci[nd] = j.Cin; dco[nd] = j.Cout; ddg[nd] = j.dgrad ? 1 : 0;
       ++nd;
       continue;
     }
-    w[nw] = j.w; out[nw] = j.out; fmt[nw] = f; dg[nw] = j.dgrad ? 1 : 0;
-    C[nw] = j.dgrad ? j.Cout : j.Cin;  // contraction channels
-    N[nw] = j.dgrad ? j.Cin : j.Cout;  // output channels
+    w[nw] = j.w; out[nw] = j.out; fmt[nw] = d.filter_format; dg[nw] = j.dgrad ? 1 : 0;
+    C[nw] = d.C;  // contraction channels
+    N[nw] = d.N;  // output channels
     ++nw;
   }
   int rc = nw ? launch_wino4_filter_batch(nw, w, out, C, N, dg, fmt, (hipStream_t)stream) : PIS_OK;
@@ -851,35 +773,14 @@ extern "C" int pis_conv3x3_dgrad_ex(const float* dz, int ldz, const float* w_fli
   PIS_CHECK_ARG(Cout % 4 == 0 && ldz % 4 == 0, "pis_conv3x3_dgrad: Cout/ldz must be multiples of 4");
   PIS_CHECK_ARG(!(flags & PIS_MASK) || mask, "pis_conv3x3_dgrad: PIS_MASK without mask");
   PIS_CHECK_ARG(!(flags & PIS_SCALE) || scale, "pis_conv3x3_dgrad: PIS_SCALE without scale");
-  IGemmArgs a{};
-  a.src = dz; a.lds = ldz; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.M = B * H * W;
-  a.Csrc = Cout; a.ntaps = 9; a.tap_mode = TAP_CONV3; a.wt = w_flip; a.ldw = 9 * Cout; a.N = Cin;
-  a.epi = EPI_NHWC; a.mask = mask; a.ldm = ldm; a.scale = scale; a.dst = dx; a.ldd = lddx;
-  a.flags = flags & (PIS_MASK | PIS_SCALE | PIS_ACCUMULATE);
-  a.w_unflipped = (flags & PIS_W_UNFLIPPED) != 0;
-  a.filter_ready = (flags & PIS_FILTER_READY) != 0;
+  IGemmArgs a = conv3x3_args(dz, ldz, w_flip, Cout, Cin, dx, lddx, B, H, W, flags & (PIS_MASK | PIS_SCALE | PIS_ACCUMULATE |
+                                                                                    PIS_W_UNFLIPPED | PIS_FILTER_READY));
+  a.mask = mask; a.ldm = ldm; a.scale = scale;
   a.is_dgrad = 1;
-  PIS_CHECK_ARG(!a.w_unflipped || (flags & PIS_WINO_PREPARED) ||
-                    (ws && direct_h3_wanted(H, W, Cout, Cin, ldz) && ws_bytes >= direct_h3_ws_bytes(Cout, Cin)) ||
-                    (ws && wino6_layer(B, H, W, Cin, Cout) && wino_ok(a) && ws_bytes >= wino_ws_bytes(B, H, W, Cout, Cin)),
-                "pis_conv3x3_dgrad_ex: PIS_W_UNFLIPPED needs the prepared F(4x4,3x3) path, the F(6x6,3x3) one or the "
-                "direct one");
-  return dispatch_conv3x3(a, B, ws, ws_bytes, (hipStream_t)stream, nullptr, (flags & PIS_WINO_PREPARED) != 0);
-}
-
-bool pis::dgrad_wino4_planned(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes) {
-  IGemmArgs a{};  // as pis_conv3x3_dgrad_ex builds it (dx / mask rows 16-B aligned)
-  a.H = H; a.W = W; a.Csrc = Cout; a.N = Cin; a.lds = ldz; a.ldd = 4; a.ldm = 4;
-  a.tap_mode = TAP_CONV3; a.epi = EPI_NHWC;
-  return wino_ok(a) && wino_tile(H, W) == 4 && wino_wanted_dims(H, W, Cout, Cin) &&
-         ws_bytes >= wino_ws_bytes(B, H, W, Cout, Cin) && !direct_h3_wanted(H, W, Cout, Cin, ldz) &&
-         !wino6_layer(B, H, W, Cin, Cout);  // an F(6x6) input gradient transforms dz itself
-}
-
-// does pis_conv3x3_dgrad_ex take the direct fp16x3 kernel (which reads the original weights
-// with PIS_W_UNFLIPPED, no flipped copy)?
-extern "C" int pis_conv3x3_dgrad_direct(int B, int H, int W, int Cin, int Cout, int ldz, size_t ws_bytes) {
-  return B > 0 && direct_h3_wanted(H, W, Cout, Cin, ldz) && ws_bytes >= direct_h3_ws_bytes(Cout, Cin);
+  const bool prepared = (flags & PIS_WINO_PREPARED) != 0;
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  return launch_conv3x3(resolve(p, a, ws, ws_bytes, false, prepared), a, B, ws, ws_bytes, (hipStream_t)stream, nullptr,
+                        prepared);
 }
 
 extern "C" int pis_convt2x2_fwd(const float* x, int ldx, const float* w_ijoc, const float* bias,

@@ -17,7 +17,7 @@
 //           Cin == 1:  n' = tap (9 of 64 columns used)
 // convT2x2: m' = (i, j, o),       A(p, ijo)   = dy[(2h+i, 2w+j)][o]
 //           n' = c,               B(p, c)     = x[p][c]
-#include "igemm.h"
+#include "conv3x3_plan.h"
 
 namespace pis {
 
@@ -618,12 +618,7 @@ size_t colsum_ws(int64_t npix, int C) {
 }
 
 // ---- wgrad planning -------------------------------------------------------
-struct WgradPlan {
-  int bm, bn, splits, pps;
-  size_t part_bytes, bias_bytes;
-};
-
-static WgradPlan plan_wgrad(int Mp, int Np, int P, int group_m, int group_n, int target_blocks = 2048) {
+WgradPlan plan_wgrad(int Mp, int Np, int P, int group_m, int group_n, int target_blocks) {
   // tile sizes must divide the per-tap group so tiles never straddle a tap
   WgradPlan p{};
   p.bm = (Mp % 128 == 0 && group_m % 128 == 0) ? 128 : 64;
@@ -648,7 +643,7 @@ static float* bias_slabs(void* ws, const WgradPlan& pl) {
   return (float*)((char*)ws + cdiv(pl.part_bytes, 256) * 256);
 }
 
-static size_t wgrad_ws_bytes(const WgradPlan& pl) { return cdiv(pl.part_bytes, 256) * 256 + pl.bias_bytes + 256; }
+size_t wgrad_ws_bytes(const WgradPlan& pl) { return cdiv(pl.part_bytes, 256) * 256 + pl.bias_bytes + 256; }
 
 // The same split-K contraction at fp32 accuracy on bf16 MFMA (bf16x6, as gemm_nt_x6_kernel in
 // winograd.hip) for plain row operands B (the Winograd weight gradient: A = E[t][Cout],
@@ -1371,43 +1366,10 @@ extern "C" int pis_colsum(const float* src, int ld, int64_t npix, int C, float* 
   return colsum(src, ld, npix, C, out, flags & PIS_ACCUMULATE, ws, ws_bytes, (hipStream_t)stream);
 }
 
-static WgradPlan conv_plan(int B, int H, int W, int Cin, int Cout) {
-  const int P = B * H * W;
-  if (Cin == 1) return plan_wgrad(Cout, 64, P, Cout, 64);
-  return plan_wgrad(Cout, 9 * Cin, P, Cout, Cin);
-}
-
-struct HaloPlan {
-  bool use;
-  int splits, seg_per_split, nseg;
-  size_t part_bytes, bias_bytes;
-};
-
-static HaloPlan halo_plan(int B, int H, int W, int Cin, int Cout) {
-  HaloPlan p{};
-  p.use = Cin % 64 == 0 && Cout % 64 == 0 && W % 16 == 0;
-  if (!p.use) return p;
-  p.nseg = (int)((int64_t)B * H * W / 16);
-  const int tiles = (Cout / 64) * (Cin / 64);
-  const size_t slab = (size_t)Cout * 9 * Cin * sizeof(float);
-  // one round of blocks (2 per CU), 512..8192 pixels per split, <= ~160 MB of partial slabs
-  int64_t splits = cdiv(std::max(64, tune_get(PIS_TUNE_WGRAD_BLOCKS)), tiles);
-  splits = std::min<int64_t>(splits, std::max<int64_t>(1, (int64_t)((160u << 20) / slab)));
-  int64_t sps = cdiv(p.nseg, splits);
-  sps = std::max<int64_t>(32, std::min<int64_t>(512, sps));
-  p.seg_per_split = (int)sps;
-  p.splits = (int)cdiv(p.nseg, sps);
-  p.part_bytes = (size_t)p.splits * slab;
-  p.bias_bytes = (size_t)p.splits * Cout * sizeof(float);
-  return p;
-}
-
 // Cin == 1 (enc1.conv0): dw[n][t] = sum_p dz[p][n] x[p + tap t], db[n] = sum_p dz[p][n].
 // K = 9 is far too short for MFMA and the pass is a read of dz (4*Cout B/px): Cout/4 lanes
 // per pixel hold 4 channels x (9 taps + bias) fp32 accumulators, the grid walks contiguous
 // pixel ranges, per-block partials go through the deterministic slab reduction.
-constexpr int C1_BLOCKS = 1024;
-
 __global__ __launch_bounds__(256) void wgrad_c1_kernel(const float* __restrict__ x, int ldx,
                                                        const float* __restrict__ dz, int ldz, int B, int H,
                                                        int W, int Cout, int64_t pix_per_block,
@@ -1511,62 +1473,6 @@ __global__ __launch_bounds__(256) void wgrad_c1_row_kernel(const float* __restri
   }
 }
 
-// Winograd weight gradient (csrc/winograd.hip), F(3x3, 4x4) when the 4x4 tile grid fits (pis_tune
-// key 11), else F(3x3, 2x2): V = B^T x B and E = G e G^T per tile, M_xi[n][c] = sum_tiles
-// E_xi[t][n] V_xi[t][c] as nxi = (m+2)^2 batched split-K GEMMs over the T tiles (slabs
-// [split][xi][Cout][Cin], one fixed-order reduction), dW = A^T M A; the bias gradient is a
-// channel sum of dz.
-struct WinoWgradPlan {
-  bool use, fused_bias, gemm_bias;
-  int m, nxi;
-  int64_t T;
-  WgradPlan gemm;
-  size_t off_E, off_part, off_M, off_cs, total;
-};
-
-static WinoWgradPlan wino_wgrad_plan(int B, int H, int W, int Cin, int Cout) {
-  WinoWgradPlan p{};
-  const int mode = tune_get(PIS_TUNE_WINOGRAD);
-  // auto (tools/bench_kernels.py --key 8 --variants 1,2 --ops wgrad, B=8): dec1.conv0 -25 %,
-  // enc2.conv0 -15 %, 64 -> 64 -2 % against the halo kernel
-  const int m = (tune_get(PIS_TUNE_WINO_F4) != 0 && H % 4 == 0 && W % 4 == 0) ? 4 : 2;
-  // F(3x3,4x4) everywhere on 4-aligned grids (64 -> 64 at 512^2: -2 % alone, -27 % with the
-  // forward's kept transform); F(3x3,2x2) only with >= 128 on both sides
-  const bool wanted = m == 4 || (Cin >= 128 && Cout >= 128);
-  p.use = mode != 0 && H % 2 == 0 && W % 2 == 0 && Cin % 64 == 0 && Cout % 64 == 0 && (mode == 2 || wanted);
-  if (!p.use) return p;
-  p.m = m;
-  p.nxi = (p.m + 2) * (p.m + 2);
-  p.T = (int64_t)B * (H / p.m) * (W / p.m);
-  // the nxi GEMMs share one launch: split so all of them together make ~target blocks
-  p.gemm = plan_wgrad(Cout, Cin, (int)p.T, Cout, Cin, std::max(16, tune_get(PIS_TUNE_WINO_WGRAD_BLOCKS) / p.nxi));
-  auto al = [](size_t b) { return cdiv(b, 256) * 256; };
-  const size_t V = al((size_t)p.nxi * p.T * Cin * 4), E = al((size_t)p.nxi * p.T * Cout * 4);
-  const size_t part = al((size_t)p.gemm.splits * p.nxi * Cout * Cin * 4), M = al((size_t)p.nxi * Cout * Cin * 4);
-  p.off_E = V;
-  p.off_part = V + E;
-  p.off_M = p.off_part + part;
-  p.off_cs = p.off_M + M;
-  // bias gradient. F(3x3,4x4): the GEMM's blocks of plane xi = 7 sum their E rows per column
-  // (E[7] = (1/3)^2 x the tile's dz sum, w4_g4 row 1) into [split][Cout] partials, which the output
-  // transform's bias blocks reduce in fixed order (no pass, no launch of its own). Else a
-  // channel-sum pass over dz.
-  p.gemm_bias = p.m == 4 && ((int64_t)Cout * Cin) % 64 == 0;
-  p.fused_bias = false;
-  const size_t cs = p.gemm_bias ? (size_t)p.gemm.splits * Cout * sizeof(float) : colsum_ws((int64_t)B * H * W, Cout);
-  p.total = p.off_cs + al(cs) + 256;
-  return p;
-}
-
-// bytes of the forward's F(4x4,3x3) input transform the weight gradient can take over
-// (pis_conv3x3_keep_bytes): the same B^T on the same 6x6 patches
-size_t wino_wgrad_keep_bytes(int B, int H, int W, int Cin, int Cout) {
-  if (direct_w_wanted(B, H, W, Cin, Cout, 4, 4)) return 0;  // the direct weight gradient reads x itself
-  if (wino6_layer(B, H, W, Cin, Cout)) return 0;  // an F(6x6) forward keeps no F(4x4) transform
-  const WinoWgradPlan p = wino_wgrad_plan(B, H, W, Cin, Cout);
-  return (p.use && p.m == 4) ? (size_t)p.nxi * p.T * Cin * sizeof(float) : 0;
-}
-
 static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw, float* db, int B, int H, int W,
                       int Cin, int Cout, int acc, const WinoWgradPlan& p, void* ws, hipStream_t s,
                       const float* keep_v = nullptr, bool e_ready = false) {
@@ -1606,25 +1512,6 @@ static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* 
   return rc;
 }
 
-// workspace of the non-direct weight-gradient paths (Winograd, halo, generic)
-static size_t wgrad_ws_nodirect(int B, int H, int W, int Cin, int Cout) {
-  const WinoWgradPlan wp = wino_wgrad_plan(B, H, W, Cin, Cout);
-  if (wp.use) return wp.total;
-  const HaloPlan hp = halo_plan(B, H, W, Cin, Cout);
-  if (hp.use) return cdiv(hp.part_bytes, 256) * 256 + hp.bias_bytes + 256;
-  if (Cin == 1 && tune_get(PIS_TUNE_C1_WGRAD) == 0)
-    return (size_t)C1_BLOCKS * 10 * Cout * sizeof(float) + 512;
-  const WgradPlan pl = conv_plan(B, H, W, Cin, Cout);
-  // Cin == 1 computes a padded [Cout][64] tile and compacts it through a staging slab
-  const size_t stage = Cin == 1 ? (size_t)Cout * 64 * sizeof(float) + 256 : 0;
-  return wgrad_ws_bytes(pl) + stage;
-}
-
-extern "C" size_t pis_conv3x3_wgrad_ws(int B, int H, int W, int Cin, int Cout) {
-  if (direct_w_wanted(B, H, W, Cin, Cout, 4, 4)) return direct_w_ws_bytes(B, H, W, Cin, Cout);
-  return wgrad_ws_nodirect(B, H, W, Cin, Cout);
-}
-
 __global__ void compact_c1_kernel(const float* __restrict__ full, float* __restrict__ dw, int Cout,
                                   int accumulate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1634,14 +1521,20 @@ __global__ void compact_c1_kernel(const float* __restrict__ full, float* __restr
   dw[i] = accumulate ? dw[i] + v : v;
 }
 
+extern "C" size_t pis_conv3x3_wgrad_ws(int B, int H, int W, int Cin, int Cout) {
+  return plan_conv3x3(B, H, W, Cin, Cout).wgrad_ws;
+}
+
 extern "C" int pis_conv3x3_wgrad_keep(const float* x, int ldx, const float* dz, int ldz, float* dw_krsc,
                                       float* db, int B, int H, int W, int Cin, int Cout, int flags, void* ws,
                                       size_t ws_bytes, const float* keep, pis_stream_t stream) {
-  const WinoWgradPlan wp = wino_wgrad_plan(B, H, W, Cin, Cout);
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  const WinoWgradPlan& wp = p.wino_w;
   const bool prepared = flags & PIS_WINO_PREPARED;
   PIS_CHECK_ARG(!prepared || (keep && wp.use && wp.m == 4),
                 "pis_conv3x3_wgrad_keep: PIS_WINO_PREPARED needs the kept-transform F(3x3,4x4) path");
-  if (!keep || !(wp.use && wp.m == 4) || (!prepared && direct_w_wanted(B, H, W, Cin, Cout, ldx, ldz)))
+  const bool direct = p.wgrad == WGRAD_DIRECT && ldx % 4 == 0 && ldz % 4 == 0;
+  if (!keep || !(wp.use && wp.m == 4) || (!prepared && direct))
     return pis_conv3x3_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, flags, ws, ws_bytes, stream);
   PIS_CHECK_ARG(x && dz && dw_krsc && ldz % 4 == 0, "pis_conv3x3_wgrad_keep: bad arguments");
   PIS_CHECK_ARG(ws && ws_bytes >= wp.total, "pis_conv3x3_wgrad_keep: workspace too small");
@@ -1653,16 +1546,15 @@ extern "C" int pis_conv3x3_bwd_prep(const float* dz, int ldz, int B, int H, int 
                                     void* ws_dgrad, size_t ws_dgrad_bytes, void* ws_wgrad, size_t ws_wgrad_bytes,
                                     pis_stream_t stream) {
   PIS_CHECK_ARG(dz && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "pis_conv3x3_bwd_prep: bad arguments");
-  if (direct_w_wanted(B, H, W, Cin, Cout, 4, ldz)) return 0;  // direct kernels read dz themselves
-  const WinoWgradPlan wp = wino_wgrad_plan(B, H, W, Cin, Cout);
-  if (tune_get(PIS_TUNE_WINO_DZ2) == 0 || !ws_dgrad || !ws_wgrad || !(wp.use && wp.m == 4) ||
-      Cin % 64 || Cout % 64 ||  // pis_conv3x3_wgrad_keep's channel contract
-      ws_wgrad_bytes < wp.total || ldz % 4 || !dgrad_wino4_planned(B, H, W, Cin, Cout, ldz, ws_dgrad_bytes))
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  const WinoWgradPlan& wp = p.wino_w;
+  if (p.prep == PREP_NONE || !ws_dgrad || !ws_wgrad || ldz % 4 || ws_wgrad_bytes < wp.total ||
+      ws_dgrad_bytes < p.dgrad.wino_ws)
     return 0;  // not applicable: the two calls transform dz themselves
   float* V = wino_v_slot(ws_dgrad, Cout, Cin);
   char* base = (char*)ws_wgrad;
   float* E = (float*)(base + wp.off_E);
-  if (wino_dgrad_t_planned(B, H, W, Cout, Cin)) {
+  if (p.prep == PREP_E_ONLY) {
     // the overlap-add input gradient (pis_tune key 51) contracts E too: one set of planes, written
     // once, read by both calls in place. pis_conv3x3_wgrad_keep with PIS_WINO_PREPARED only reads
     // [off_E, off_part) (it writes the split slabs, M and the bias partials behind it).
@@ -1670,8 +1562,8 @@ extern "C" int pis_conv3x3_bwd_prep(const float* dz, int ldz, int B, int H, int 
     if (!rc) wino_prep_record(ws_dgrad, B, H, W, Cout, Cin, false, E);
     return rc ? rc : 1;
   }
-  float* tmax = wino_fused_h3_planned(B, H, W, Cout, Cin) ? wino_tmax_slot(ws_dgrad, B, H, W, Cout, Cin) : nullptr;
-  // (no bias partials: the weight gradient's GEMM sums them from E, wino_wgrad_plan gemm_bias)
+  float* tmax = p.prep == PREP_DZ2_TMAX ? wino_tmax_slot(ws_dgrad, B, H, W, Cout, Cin) : nullptr;
+  // (no bias partials: the weight gradient's GEMM sums them from E, WinoWgradPlan gemm_bias)
   const int rc = launch_wino_dz2(dz, ldz, B, H, W, Cout, V, E, nullptr, (hipStream_t)stream, tmax);
   // the dgrad_ex that consumes this V checks that it decides the same tile-maxima format
   if (!rc) wino_prep_record(ws_dgrad, B, H, W, Cout, Cin, tmax != nullptr);
@@ -1683,30 +1575,22 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
                                  void* ws, size_t ws_bytes, pis_stream_t stream) {
   PIS_CHECK_ARG(x && dz && dw_krsc && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0,
                 "pis_conv3x3_wgrad: bad arguments");
-  PIS_CHECK_ARG(ws && ws_bytes >= pis_conv3x3_wgrad_ws(B, H, W, Cin, Cout),
-                "pis_conv3x3_wgrad: workspace too small");
+  // (a shape outside the channel contract plans no workspace: it is rejected right below)
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  PIS_CHECK_ARG(ws && ws_bytes >= p.wgrad_ws, "pis_conv3x3_wgrad: workspace too small");
   PIS_CHECK_ARG(Cout % 64 == 0 && (Cin == 1 || Cin % 64 == 0),
                 "pis_conv3x3_wgrad: Cout must be a multiple of 64 and Cin 1 or a multiple of 64");
   PIS_CHECK_ARG((Cin == 1 || ldx % 4 == 0) && ldz % 4 == 0, "pis_conv3x3_wgrad: ld must be multiples of 4");
   hipStream_t s = (hipStream_t)stream;
   const int acc = flags & PIS_ACCUMULATE;
-  // the direct kernel reads x and dz as float4s: 16-B aligned base pointers (a channel slice at an
-  // offset that is not a multiple of 4 floats falls through to the Winograd / halo kernels)
-  if (direct_w_wanted(B, H, W, Cin, Cout, ldx, ldz)) {
-    // (a workspace smaller than the direct kernel's slabs falls through to the kernels below, as
-    // does a misaligned operand)
-    if (((uintptr_t)x & 15) == 0 && ((uintptr_t)dz & 15) == 0 && ws_bytes >= direct_w_ws_bytes(B, H, W, Cin, Cout))
-      return launch_direct_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, ws, ws_bytes, s);
-    PIS_CHECK_ARG(ws_bytes >= wgrad_ws_nodirect(B, H, W, Cin, Cout),
-                  "pis_conv3x3_wgrad: x / dz not 16-byte aligned or workspace below the direct kernel's; "
-                  "the non-direct fallback needs a larger "
-                  "workspace than pis_conv3x3_wgrad_ws reports for this (direct) layer");
-  }
-  const WinoWgradPlan wp = wino_wgrad_plan(B, H, W, Cin, Cout);
-  if (wp.use && ldx % 4 == 0 && ws_bytes >= wp.total)
-    return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, wp, ws, s);
-  const HaloPlan hp = halo_plan(B, H, W, Cin, Cout);
-  if (hp.use && ldx % 4 == 0) {
+  const WgradAlgo algo = resolve_wgrad(p, x, dz, ws_bytes);
+  if (algo == WGRAD_NONE) return PIS_ERR_ARG;
+  if (algo == WGRAD_DIRECT)
+    return launch_direct_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, ws, ws_bytes, s);
+  if (algo == WGRAD_WINO4 || algo == WGRAD_WINO2)
+    return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, p.wino_w, ws, s);
+  if (algo == WGRAD_HALO) {
+    const HaloPlan& hp = p.halo_w;
     W3Args a{};
     a.x = x; a.ldx = ldx; a.dz = dz; a.ldz = ldz;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
@@ -1726,7 +1610,7 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
                                 acc, s);
     return rc;
   }
-  if (Cin == 1 && tune_get(PIS_TUNE_C1_WGRAD) == 0) {
+  if (algo == WGRAD_C1_STREAM) {
     PIS_CHECK_ARG(Cout <= 1024 && Cout % 4 == 0, "pis_conv3x3_wgrad: Cin == 1 needs Cout % 4 == 0, <= 1024");
     const int64_t npix = (int64_t)B * H * W;
     const int64_t ppb = cdiv(npix, C1_BLOCKS);
@@ -1748,7 +1632,7 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
     if (!rc) rc = reduce_slabs2(part, nslab, (int64_t)9 * Cout, dw_krsc, db ? part_b : nullptr, nslab, Cout, db, acc, s);
     return rc;
   }
-  const WgradPlan pl = conv_plan(B, H, W, Cin, Cout);
+  const WgradPlan& pl = p.gemm_w;  // WGRAD_GENERIC, WGRAD_C1_MFMA
   WgradArgs a{};
   a.a = dz; a.lda = ldz; a.a_up2 = 0; a.Ca = Cout;
   a.b = x; a.ldb = ldx; a.b_mode = Cin == 1 ? B_CONV3_C1 : B_CONV3; a.Cb = Cin;

@@ -2556,19 +2556,6 @@ static void launch_wino4_filter(const IGemmArgs& a, int N, int C, float* U, int 
 // the fused 64 -> 64 kernel's arithmetic (pis_tune key 22): fp16x3 planes instead of bf16x6
 static bool wino_gemm_out_h3() { return tune_get(PIS_TUNE_WINO_GEMM_OUT_H3) != 0; }
 
-// fused path eligibility (pis_tune key 15): F(4x4), bf16x6 GEMMs, 64 -> 64 channels. Measured
-// (tools/bench_kernels.py --key 15, C2): enc1.conv1 forward 1.13 -> 0.98 ms, input gradient
-// 1.30 -> 1.13 ms; with 128 input or output channels (dec1.conv0, enc2.conv0) it is 2-8 % slower
-// than the separate GEMM + output transform, so those keep the 3-pass pipeline.
-static bool wino_gemm_out_wanted(int m, int64_t T, int C, int N) {
-  // N = 128 (64-channel contractions into 128 outputs: enc2.conv0 forward, dec1.conv0 input
-  // gradient) with pis_tune key 26: two blocks per tile group, V read twice (from L2), M never
-  return m == 4 && tune_get(PIS_TUNE_WINO_GEMM_OUT) != 0 && tune_get(PIS_TUNE_WINO_TILE) >= 3 && T % 32 == 0 &&
-         T >= 2 * (int64_t)C &&  // the filter planes fit in the M region
-         (C == 64 || (C == 128 && tune_get(PIS_TUNE_FUSED_K128) != 0)) &&
-         (N == 64 || (N % 64 == 0 && N <= 64 * (1 << tune_get(PIS_TUNE_FUSED_WIDE))));
-}
-
 static int launch_wino_gemm_out(const float* V, const __bf16* Up, const IGemmArgs& a, int B, int64_t T,
                                 hipStream_t s, const float* tmax) {
   // 8 waves: 32 tiles x 64 channels per block; G such groups per block where they divide
@@ -2632,15 +2619,10 @@ static int launch_wino_gemm_out(const float* V, const __bf16* Up, const IGemmArg
 }
 
 
-// does a contraction of C channels into N outputs at B x H x W take the fused F(4x4) kernel?
-bool wino_fused_wanted(int B, int H, int W, int C, int N) {
-  return wino_tile(H, W) == 4 && wino_gemm_out_wanted(4, (int64_t)B * (H / 4) * (W / 4), C, N);
-}
-
 static int64_t wino6_tiles(int B, int H, int W) { return (int64_t)B * ((H + 5) / 6) * ((W + 5) / 6); }
 
 // U (64 N C), V (64 T C), M (64 T N) of one F(6x6,3x3) call
-static size_t wino6_ws_bytes(int B, int H, int W, int C, int N) {
+size_t wino6_ws_bytes(int B, int H, int W, int C, int N) {
   const int64_t T = wino6_tiles(B, H, W);
   return (size_t)64 * ((int64_t)N * C + T * C + T * N) * sizeof(float) + 1024;
 }
@@ -2706,57 +2688,48 @@ static int launch_wino6(const IGemmArgs& a, int B, void* ws, hipStream_t s) {
   return launch_status("wino6_output");
 }
 
-// F(4x4,3x3) when the 4x4 tile grid fits and pis_tune key 11 allows it, else F(2x2,3x3)
-int wino_tile(int H, int W) { return (tune_get(PIS_TUNE_WINO_F4) != 0 && H % 4 == 0 && W % 4 == 0) ? 4 : 2; }
-
-bool wino_ok(const IGemmArgs& a) {
-  return a.tap_mode == TAP_CONV3 && a.epi == EPI_NHWC && a.H % 2 == 0 && a.W % 2 == 0 && a.Csrc % 4 == 0 &&
-         a.N % 4 == 0 && a.lds % 4 == 0 && a.ldd % 4 == 0 && (!(a.flags & PIS_MASK) || a.ldm % 4 == 0);
-}
-
 // where launch_wino3x3 keeps V inside its workspace (pis_conv3x3_bwd_prep writes it there)
 float* wino_v_slot(void* ws, int C, int N) { return (float*)ws + (size_t)36 * N * C; }
 
-size_t wino_ws_bytes(int B, int H, int W, int C, int N) {
-  const int m = wino_tile(H, W), nxi = (m + 2) * (m + 2);
+size_t wino_ws_bytes(int m, int B, int H, int W, int C, int N) {
+  const int nxi = (m + 2) * (m + 2);
   const int64_t T = (int64_t)B * (H / m) * (W / m);
   // + the fp16x3 tile maxima after M: per (tile, 64-channel chunk) of V (wino_tmax_slot)
   const int64_t extra = T * ((C + 63) / 64) + 8;
-  const size_t f4 = (size_t)(nxi * ((int64_t)N * C + T * C + T * N) + extra) * sizeof(float) + 1024;
-  return wino6_layer(B, H, W, C, N) ? std::max(f4, wino6_ws_bytes(B, H, W, C, N)) : f4;
+  return (size_t)(nxi * ((int64_t)N * C + T * C + T * N) + extra) * sizeof(float) + 1024;
 }
 
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, const float** e);
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, const float** e);
 
-// pis_tune key 51: an F(4x4,3x3) input gradient on the batched GEMM (C = Cout contraction channels,
-// N = Cin; not the fused contraction, and the callers exclude the direct and F(6x6) layers) contracts
-// the weight gradient's E with U' and ends in the overlap-add transform (wino4_output_t_kernel)
-bool wino_dgrad_t_planned(int B, int H, int W, int C, int N) {
-  if (tune_get(PIS_TUNE_WINO_DGRAD_T) == 0 || wino_tile(H, W) != 4) return false;
-  return !wino_gemm_out_wanted(4, (int64_t)B * (H / 4) * (W / 4), C, N);
-}
-
-// a describes the direct conv (src/lds = input, wt/ldw = KRSC weights, N outputs, epilogue)
-int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v, bool v_ready) {
+// a describes the direct conv (src/lds = input, wt/ldw = KRSC weights, N outputs, epilogue); algo:
+// the pipeline to run, as conv3x3_plan.h resolved it for this call (even H and W, 4-aligned
+// channels and strides; F(4x4) / F(6x6): H, W % 4 == 0)
+int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v, bool v_ready) {
   const int C = a.Csrc, N = a.N;
-  const int m = wino_tile(a.H, a.W), nxi = (m + 2) * (m + 2);
+  const int m = algo == ALGO_WINO2 ? 2 : 4, nxi = (m + 2) * (m + 2);
+  if (a.H % m || a.W % m || C % 4 || N % 4 || a.lds % 4 || a.ldd % 4 ||
+      !(algo == ALGO_WINO2 || algo == ALGO_WINO4_GEMM || algo == ALGO_WINO4_FUSED || algo == ALGO_WINO6 ||
+        (algo == ALGO_WINO4_DGRAD_T && a.is_dgrad)))
+    return set_error("launch_wino3x3: not a Winograd shape or algorithm"), PIS_ERR_ARG;
   const int64_t T = (int64_t)B * (a.H / m) * (a.W / m);
+  if ((algo == ALGO_WINO6 && (keep_v || v_ready || N % 64 || C % 32)) ||
+      (algo == ALGO_WINO4_FUSED && ((C != 64 && C != 128) || N % 64 || T % 32 || T < 2 * (int64_t)C)))
+    return set_error("launch_wino3x3: the shape does not fit the planned pipeline"), PIS_ERR_ARG;
   float* U = (float*)ws;
   float* V = U + (size_t)nxi * N * C;
   float* Mt = V + (size_t)nxi * T * C;
   if (keep_v && m == 4) V = keep_v;
   const float* e_prep = nullptr;  // a prepared overlap-add input gradient's E (in the weight gradient's workspace)
   if (v_ready && m == 4) {
-    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N, &e_prep);
+    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N, algo, &e_prep);
     if (rc) return rc;
   }
   // F(6x6,3x3): the deep layers' forward and input gradient (no kept or prepared F(4x4) transforms)
-  if (m == 4 && !keep_v && !v_ready && wino6_layer(B, a.H, a.W, C, N) && N % 64 == 0 && C % 32 == 0)
-    return launch_wino6(a, B, ws, s);
+  if (algo == ALGO_WINO6) return launch_wino6(a, B, ws, s);
   const double flop = 2.0 * nxi * (double)T * N * C;
   if (a.filter_ready && m != 4)
     return set_error("launch_wino3x3: PIS_FILTER_READY needs the F(4x4,3x3) GEMM path"), PIS_ERR_ARG;
-  if (wino_gemm_out_wanted(m, T, C, N)) {
+  if (algo == ALGO_WINO4_FUSED) {
     // the pre-split filter planes (1.5x U's bytes) go where M would have been
     __bf16* Up = reinterpret_cast<__bf16*>(Mt);
     if (a.filter_ready) Up = const_cast<__bf16*>(reinterpret_cast<const __bf16*>(a.wt));
@@ -2778,7 +2751,7 @@ int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* ke
     return set_error("launch_wino3x3: unflipped weights need F(4x4,3x3) and 32-aligned channels"), PIS_ERR_ARG;
   // the overlap-add input gradient: the GEMM's A operand is E (the call's own, in V's place, or
   // the one pis_conv3x3_bwd_prep left for the weight gradient too), its filter U'
-  const bool dgrad_t = m == 4 && a.is_dgrad && wino_dgrad_t_planned(B, a.H, a.W, C, N);
+  const bool dgrad_t = algo == ALGO_WINO4_DGRAD_T;
   if (dgrad_t) {
     if (a.filter_ready) U = const_cast<float*>(a.wt);
     else launch_wino4_filter(a, N, C, U, 0, nullptr, s, false, 1);
@@ -2863,16 +2836,6 @@ int launch_wino3x3(const IGemmArgs& a, int B, void* ws, hipStream_t s, float* ke
   return launch_status("wino_output");
 }
 
-// the F(4x4,3x3) filter transform a conv call with these shapes consumes (pis_conv3x3_filter):
-// 1 fp32 U[36][N][C] for the batched GEMMs, 2 the bf16x6 planes of the fused 64 -> 64
-// contraction, 0 none (not the F(4x4,3x3) GEMM path). C = contraction channels, N = outputs.
-int wino_filter_format(int B, int H, int W, int C, int N, bool kept) {
-  if (wino_tile(H, W) != 4) return 0;
-  const int64_t T = (int64_t)B * (H / 4) * (W / 4);
-  if (wino_gemm_out_wanted(4, T, C, N)) return 2;
-  return 1;
-}
-
 int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s) {
   IGemmArgs a{};
   a.wt = w; a.ldw = 9 * C; a.w_unflipped = dgrad;
@@ -2881,7 +2844,7 @@ int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format
   if (format == 2 && wino_gemm_out_h3() && (C % 64 || N % 4))
     return set_error("pis_conv3x3_filter: fp16x3 planes need 64 x k contraction channels"), PIS_ERR_ARG;
   if (format == 2) launch_wino4_filter(a, N, C, nullptr, 0, reinterpret_cast<__bf16*>(out), s, wino_gemm_out_h3());
-  else  // format 1 of an input gradient: the batched GEMM, so U' with key 51 (wino_dgrad_t_planned)
+  else  // format 1 of an input gradient: the batched GEMM, so U' with key 51 (ALGO_WINO4_DGRAD_T)
     launch_wino4_filter(a, N, C, reinterpret_cast<float*>(out), 0, nullptr, s, false,
                         dgrad && tune_get(PIS_TUNE_WINO_DGRAD_T) != 0);
   return launch_status("wino_filter");
@@ -2975,8 +2938,8 @@ int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float*
   return launch_status("wino_dz2");
 }
 
-// pis_conv3x3_bwd_prep decides whether its V carries tile maxima (wino_fused_h3_planned) from the
-// tune state at ITS call; the dgrad_ex that consumes the V decides again at its own. A changed
+// pis_conv3x3_bwd_prep decides whether its V carries tile maxima (the plan's PrepKind) from the
+// tune state at ITS call; the dgrad_ex that consumes the V plans again at its own. A changed
 // knob in between would make the fused fp16x3 kernel read stale or unwritten scales, so every prep
 // is recorded (workspace, shape, decision) and a prepared dgrad must find a matching record.
 namespace {
@@ -2997,16 +2960,17 @@ void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tm
   g_prep_next = (g_prep_next + 1) % 16;
 }
 
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, const float** e) {
+// algo: what this call resolved to; the fused contraction reads tile maxima in fp16x3 (key 22)
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, const float** e) {
   for (const auto& r : g_prep)
     if (r.ws == ws && r.B == B && r.H == H && r.W == W && r.C == C && r.N == N) {
-      if ((r.e != nullptr) != wino_dgrad_t_planned(B, H, W, C, N))
+      if ((r.e != nullptr) != (algo == ALGO_WINO4_DGRAD_T))
         return set_error("PIS_WINO_PREPARED: pis_conv3x3_bwd_prep wrote %s but this call's kernel choice reads %s "
                          "(a pis_tune knob changed in between)",
                          r.e ? "E alone" : "V(dz)", r.e ? "V(dz)" : "E"),
                PIS_ERR_ARG;
       *e = r.e;
-      if (r.tmax != wino_fused_h3_planned(B, H, W, C, N))
+      if (r.tmax != (algo == ALGO_WINO4_FUSED && wino_gemm_out_h3()))
         return set_error("PIS_WINO_PREPARED: pis_conv3x3_bwd_prep wrote %s tile maxima but this call's kernel "
                          "choice needs %s (a pis_tune knob changed in between)",
                          r.tmax ? "" : "no", r.tmax ? "none" : "them"),
@@ -3020,14 +2984,6 @@ static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, co
 float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N) {
   const int64_t T = (int64_t)B * (H / 4) * (W / 4);
   return (float*)ws + (size_t)36 * ((int64_t)N * C + T * C + T * N);
-}
-
-// the dgrad of these shapes (C contraction = Cout, N = Cin) reads tile maxima (the fused fp16x3
-// kernel): its V producer (pis_conv3x3_bwd_prep) must write them
-bool wino_fused_h3_planned(int B, int H, int W, int C, int N) {
-  if (wino_tile(H, W) != 4) return false;
-  const int64_t T = (int64_t)B * (H / 4) * (W / 4);
-  return wino_gemm_out_wanted(4, T, C, N) && wino_gemm_out_h3();
 }
 
 int launch_wino_wgrad_out(const float* M, int N, int C, float* dw, int accumulate, hipStream_t s, int m,
