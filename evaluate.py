@@ -69,12 +69,21 @@ def parse_args(argv=None):
                     help="reaction threshold a of the residual for --physics-metrics, in (0, 1) (default: 0.5)")
     ap.add_argument("--physics-epsilon", type=float, default=0.05, metavar="F",
                     help="interface width of the phase-field energy for --physics-metrics (default: 0.05)")
+    ap.add_argument("--surface-metrics", action="store_true",
+                    help="also report surface-distance metrics: the percentile Hausdorff distance (HD95), the average "
+                         "symmetric surface distance and the surface Dice at a tolerance (distance transform on the GPU)")
+    ap.add_argument("--surface-percentile", type=int, default=95, metavar="N",
+                    help="percentile of the Hausdorff distance for --surface-metrics, 1..100 (default: 95)")
+    ap.add_argument("--surface-tolerance", type=int, default=2, metavar="N",
+                    help="tolerance in pixels of the surface Dice for --surface-metrics, >= 0 (default: 2)")
     args = ap.parse_args(argv)
     args.refine_preset = refine_from_args(ap, args)
     if args.physics_metrics and not (args.physics_diffusion >= 0 and 0 < args.physics_threshold_a < 1
                                      and args.physics_epsilon > 0):
         ap.error("--physics-metrics: --physics-diffusion >= 0, --physics-threshold-a in (0, 1) and "
                  "--physics-epsilon > 0 are needed")
+    if args.surface_metrics and not (1 <= args.surface_percentile <= 100 and 0 <= args.surface_tolerance <= 46340):
+        ap.error("--surface-metrics: --surface-percentile in 1..100 and --surface-tolerance in 0..46340 are needed")
     return args
 
 
@@ -102,6 +111,9 @@ def main(argv=None):
     if args.physics_metrics:
         common.update(physics_metrics=True, physics_D=args.physics_diffusion, physics_a=args.physics_threshold_a,
                       physics_eps=args.physics_epsilon)
+    if args.surface_metrics:
+        common.update(surface_metrics=True, surface_percentile=args.surface_percentile,
+                      surface_tolerance=args.surface_tolerance)
     if args.repeated:
         base = sorted(glob(args.baseline))
         pde = sorted(glob(args.pde))

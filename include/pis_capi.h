@@ -255,7 +255,16 @@ int pis_version(void);
                                 faster there and 2 % slower at 2048^2 (tools/bench_evolve.py,
                                 profiles/pde_evolve.txt). The key may change between any two calls (the
                                 workspace does not depend on it) */
-#define PIS_TUNE_NKEYS 55
+#define PIS_TUNE_EDT_PRUNE 55 /* pis_edt_sq / pis_surface_distances (csrc/distance.hip): what the row pass's outward
+                                 search skips. 0: nothing; 1: whole 64-column blocks of radii, by the minimum of the
+                                 column distances over the segments a block touches; 3: and 8-column steps, by the
+                                 minima of the aligned groups a step touches. Anything else is PIS_ERR_ARG. Every
+                                 value gives the same integers and uses the same workspace (the key may change
+                                 between any two calls). Default 3: the lowest time of pis_edt_sq on disc-mask
+                                 boundaries at 8 x 512^2 (the rule, fixed before measuring), 150.4 us against 156.3
+                                 (1) and 158.3 (0); one set pixel in a corner of 2048^2 takes 421.9 / 458.2 /
+                                 3247.5 us (tools/bench_surface.py, profiles/surface_metrics.txt) */
+#define PIS_TUNE_NKEYS 56
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -846,6 +855,30 @@ int pis_pde_evolve(const float* u, const float* u0, float* out, uint8_t* mask, i
 size_t pis_pde_energies_ws(int B, int H, int W);
 int pis_pde_energies(const float* u, int B, int H, int W, float D, float a, float eps, double* out_f64,
                      int64_t* out_i64, void* ws, size_t ws_bytes, pis_stream_t stream);
+
+/* ---- exact squared Euclidean distance transform of a batch of binary images, and the per-pixel
+ * surface distances between two boundary maps (no reference counterpart;
+ * evaluate.py:distance_transform_sq_np / surface_distances) ----
+ * pis_edt_sq: set is (N, H, W) uint8, a pixel belongs to the set of its image when its byte is not 0.
+ *   d2[n][y][x] = min over the set pixels (y', x') of image n of (y - y')^2 + (x - x')^2     int32 (N, H, W)
+ * 0 inside the set, PIS_EDT_NONE at every pixel of an image whose set is empty. Exact (the largest
+ * value is 2 * 4095^2 < 2^26). Three launches on `stream` whatever the data (column masks, column
+ * distances, one wave per row), no host synchronisation, no atomics: bitwise reproducible.
+ * pis_surface_distances: bnd_p, bnd_t are (B, H, W) uint8 boundary maps (pis_boundary_metrics writes
+ * them). The transforms of all 2 B maps run in the same three launches, evaluated only where needed:
+ *   d2_pt[b][q] = the transform of bnd_t[b] at q where bnd_p[b][q] != 0, else -1           int32 (B, H, W)
+ *   d2_tp[b][q] = the transform of bnd_p[b] at q where bnd_t[b][q] != 0, else -1
+ * so a boundary pixel whose opposite boundary is empty holds PIS_EDT_NONE.
+ * N, B >= 1 (B <= 2^24), 1 <= H, W <= 4096; anything else and a NULL pointer are PIS_ERR_ARG, a
+ * workspace below pis_edt_ws(N, H, W) / pis_surface_distances_ws(B, H, W) bytes PIS_ERR_WORKSPACE (both
+ * answer 0 for an unsupported shape). No state in ws between calls; the outputs may not overlap ws. */
+#define PIS_EDT_NONE 0x7FFFFFFF
+size_t pis_edt_ws(int N, int H, int W);
+int pis_edt_sq(const uint8_t* set, int N, int H, int W, int32_t* d2, void* ws, size_t ws_bytes,
+               pis_stream_t stream);
+size_t pis_surface_distances_ws(int B, int H, int W);
+int pis_surface_distances(const uint8_t* bnd_p, const uint8_t* bnd_t, int B, int H, int W, int32_t* d2_pt,
+                          int32_t* d2_tp, void* ws, size_t ws_bytes, pis_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,13 +13,14 @@ __version__ = "0.2.0"
 from .dataset import (AffineAugment, CellSegmentationDataset, DeviceCachedLoader, SyntheticDiscDataset,  # noqa: E402
                       pack_samples)
 from .evaluate import (ProbabilityTable, best_threshold_batch, boundary_counts,  # noqa: E402
-                       compare_models_statistically, compute_aji_batch, compute_auroc_batch,
+                       compare_models_statistically, compute_aji_batch, compute_assd_batch, compute_auroc_batch,
                        compute_average_precision_batch, compute_boundary_f1, compute_boundary_f1_batch,
                        compute_brier_batch, compute_ece_batch, compute_hausdorff_distance,
-                       compute_hausdorff_distance_batch, compute_iou, compute_iou_batch, compute_object_f1_batch,
-                       compute_statistics, evaluate_model, evaluate_on_test_set, extract_boundaries_device,
-                       format_metric_report, label_components, object_counts, probability_table,
-                       threshold_sweep_counts)
+                       compute_hausdorff_distance_batch, compute_hausdorff_percentile_batch, compute_iou,
+                       compute_iou_batch, compute_object_f1_batch, compute_statistics, compute_surface_dice_batch,
+                       distance_transform_sq, distance_transform_sq_np, evaluate_model, evaluate_on_test_set,
+                       extract_boundaries_device, format_metric_report, label_components, object_counts,
+                       probability_table, surface_distances, threshold_sweep_counts)
 from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
@@ -44,4 +45,6 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "probability_table", "threshold_sweep_counts", "compute_auroc_batch", "compute_average_precision_batch",
            "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable",
            "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np",
-           "PDERefine", "evolve", "evolve_np", "energies", "energies_np"]
+           "PDERefine", "evolve", "evolve_np", "energies", "energies_np",
+           "distance_transform_sq", "distance_transform_sq_np", "surface_distances",
+           "compute_hausdorff_percentile_batch", "compute_assd_batch", "compute_surface_dice_batch"]

@@ -23,6 +23,7 @@ PIS_TUNE_LAST_WGRAD_MAIN = 42  # include/pis_capi.h: host schedule knob (unet.py
 PIS_TUNE_DIRECT_MFMA16 = 53  # include/pis_capi.h: MFMA shape of the direct fp16x3 kernels (bit 0 forward / input gradient, bit 1 weight gradient)
 PIS_TUNE_PROB_VARIANT = 52 # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
 PIS_TUNE_EVOLVE_T = 54  # include/pis_capi.h: steps per launch of pis_pde_evolve (1, 2, 4 or 8)
+PIS_TUNE_EDT_PRUNE = 55  # include/pis_capi.h: what the distance transform's outward search skips (0, 1 or 3)
 PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
@@ -123,6 +124,10 @@ _SIGNATURES = {
                        c_int),
     "pis_pde_energies_ws": ([I, I, I], c_size_t),
     "pis_pde_energies": ([P, I, I, I, c_float, c_float, c_float, P, P, P, Z, P], c_int),
+    "pis_edt_ws": ([I, I, I], c_size_t),
+    "pis_edt_sq": ([P, I, I, I, P, P, Z, P], c_int),
+    "pis_surface_distances_ws": ([I, I, I], c_size_t),
+    "pis_surface_distances": ([P, P, I, I, I, P, P, P, Z, P], c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

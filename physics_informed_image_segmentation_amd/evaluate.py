@@ -40,6 +40,12 @@
   tensors, numpy otherwise; == in tests/test_probability_gpu.py). They are the metrics of the
   probabilities rounded up to 16 fractional bits, with thresholds and rank ties on a 1 / 1024 grid.
   ``evaluate_model(probability_metrics=True)`` adds them; ``ProbabilityTable`` pools a loader.
+* Surface-distance metrics (no reference counterpart): the exact squared Euclidean distance transform
+  (``distance_transform_sq``: csrc/distance.hip, pis_edt_sq for CUDA tensors, scipy otherwise; ==
+  in tests/test_surface_gpu.py), the per-pixel distances between the two boundary maps
+  (``surface_distances``, pis_surface_distances) and from them the percentile Hausdorff distance
+  (HD95), the average symmetric surface distance and the surface Dice at a tolerance.
+  ``evaluate_model(surface_metrics=True)`` adds them.
 """
 from __future__ import annotations
 
@@ -679,6 +685,208 @@ class ProbabilityTable:
         return float(compute_brier_batch(self._batch())[0])
 
 
+# ----------------------------------------------------------------------------
+# Distance transform and surface-distance metrics: HD95, ASSD, surface Dice (csrc/distance.hip)
+# ----------------------------------------------------------------------------
+# Definitions (include/pis_capi.h). The squared Euclidean distance transform of a set is,
+# per pixel, the smallest (y - y')^2 + (x - x')^2 over the set's pixels: an exact int32, 0 inside the
+# set, EDT_NONE everywhere when the set is empty. With Bp, Bt the boundary maps of a sample
+# (``extract_boundaries`` of p > threshold and of t > 0), the surface distances are the two tables
+#   d2_pt[q] = the transform of Bt at q for q in Bp, -1 elsewhere;  d2_tp the mirror image
+# and the three scores are torch arithmetic on them (the same code for both backends):
+#   Hausdorff percentile  per direction the nearest-rank percentile of the n distances, the
+#                         k-th smallest with k = (percentile n + 99) // 100; sqrt of the larger one
+#   ASSD                  (sum_Bp sqrt(d2_pt) + sum_Bt sqrt(d2_tp)) / (n_p + n_t)
+#   surface Dice          (m_p + m_t + smooth) / (n_p + n_t + smooth), m = #[0 <= d2 <= tolerance^2]
+# The first two are inf when either boundary is empty, as compute_hausdorff_distance is.
+
+EDT_NONE = 2 ** 31 - 1
+# the per-image arrays evaluate_model(surface_metrics=True) adds, in this order
+SURFACE_METRIC_KEYS = ("hausdorff_percentile_distances", "assd_distances", "surface_dice_scores")
+
+
+def _check_backend(backend: str) -> None:
+    if backend not in ("auto", "host", "device"):
+        raise ValueError(f"backend must be 'auto', 'host' or 'device', got {backend!r}")
+
+
+def _check_percentile(percentile: int) -> int:
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, np.integer)) or not 1 <= percentile <= 100:
+        raise ValueError(f"percentile must be an integer in 1..100, got {percentile!r}")
+    return int(percentile)
+
+
+def _check_surface_tolerance(tolerance: int) -> int:
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, np.integer)) or not 0 <= tolerance <= 46340:
+        raise ValueError(f"tolerance must be an integer in 0..46340, got {tolerance!r}")
+    return int(tolerance)
+
+
+def distance_transform_sq_np(mask: np.ndarray) -> np.ndarray:
+    """The definition of record: the squared Euclidean distance transform of every (H, W) image of
+    ``mask`` ((..., H, W); the set is ``mask > 0``, so NaN is outside) as int32 (B, H, W), by
+    scipy.ndimage.distance_transform_edt, squared and rounded (exact: the squares are integers far
+    below 2^53). An image with an empty set is EDT_NONE everywhere."""
+    a = np.asarray(mask)
+    if a.ndim < 2:
+        raise ValueError(f"need (..., H, W), got {a.shape}")
+    with np.errstate(invalid="ignore"):
+        s = a.reshape(-1, a.shape[-2], a.shape[-1]) > 0
+    out = np.full(s.shape, EDT_NONE, np.int32)
+    for i, m in enumerate(s):
+        if m.any():
+            out[i] = np.rint(ndimage.distance_transform_edt(~m) ** 2).astype(np.int32)
+    return out
+
+
+def _edt_device(sets: torch.Tensor) -> torch.Tensor:
+    """One pis_edt_sq call (three launches) on the current stream; ``sets``: uint8 (B, H, W) on the GPU."""
+    _hip.require_cuda(sets, "distance_transform_sq")
+    B, H, W = sets.shape
+    with torch.cuda.device(sets.device):
+        nbytes = _hip.lib().pis_edt_ws(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"distance_transform_sq: unsupported shape B={B} H={H} W={W} (B >= 1, 1 <= H, W <= 4096)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=sets.device)
+        d2 = torch.empty((B, H, W), dtype=torch.int32, device=sets.device)
+        _hip.call("pis_edt_sq", _hip.ptr(sets), B, H, W, _hip.ptr(d2), _hip.ptr(ws), nbytes,
+                  _hip.stream_handle(sets.device))
+    return d2
+
+
+def distance_transform_sq(mask: torch.Tensor, backend: str = "auto") -> torch.Tensor:
+    """Squared Euclidean distance from every pixel to the nearest pixel of the set ``mask > 0`` of
+    its image, int32 (B, H, W) for a (B, 1, H, W), (B, H, W) or (H, W) input: 0 inside the set,
+    EDT_NONE for an image with an empty set. CUDA tensors: on their device, one pis_edt_sq call, no
+    host synchronisation. CPU tensors (and ``backend="host"``): ``distance_transform_sq_np``, a CPU
+    tensor; the two agree exactly."""
+    if _use_device(backend, mask, mask):
+        m = mask.detach()
+        if m.dim() < 2:
+            raise ValueError(f"need (..., H, W), got {tuple(m.shape)}")
+        return _edt_device((m.reshape(-1, m.shape[-2], m.shape[-1]) > 0).to(torch.uint8).contiguous())
+    return torch.from_numpy(distance_transform_sq_np(_bhw(mask).cpu().numpy()))
+
+
+def _surface_host(predictions: torch.Tensor, targets: torch.Tensor, threshold: float) -> Tuple[np.ndarray, np.ndarray]:
+    p, t = _bhw(predictions).cpu().numpy(), _bhw(targets).cpu().numpy()
+    if p.shape != t.shape:
+        raise ValueError(f"predictions {p.shape} and targets {t.shape} differ")
+    with np.errstate(invalid="ignore"):
+        fp, ft = p > threshold, t > 0
+    bp = np.stack([extract_boundaries(m) for m in fp]) > 0
+    bt = np.stack([extract_boundaries(m) for m in ft]) > 0
+    return (np.where(bp, distance_transform_sq_np(bt), np.int32(-1)),
+            np.where(bt, distance_transform_sq_np(bp), np.int32(-1)))
+
+
+def _surface_device(predictions: torch.Tensor, targets: torch.Tensor, threshold: float
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pis_boundary_metrics call for the two boundary maps, one pis_surface_distances call."""
+    _, bp, bt = _boundary_device(predictions, targets, threshold, 0, maps=True)
+    B, H, W = bp.shape
+    with torch.cuda.device(bp.device):
+        nbytes = _hip.lib().pis_surface_distances_ws(B, H, W)
+        if nbytes == 0:
+            raise ValueError(f"surface_distances: unsupported shape B={B} H={H} W={W} (B >= 1, 1 <= H, W <= 4096)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=bp.device)
+        d2_pt = torch.empty((B, H, W), dtype=torch.int32, device=bp.device)
+        d2_tp = torch.empty((B, H, W), dtype=torch.int32, device=bp.device)
+        _hip.call("pis_surface_distances", _hip.ptr(bp), _hip.ptr(bt), B, H, W, _hip.ptr(d2_pt), _hip.ptr(d2_tp),
+                  _hip.ptr(ws), nbytes, _hip.stream_handle(bp.device))
+    return d2_pt, d2_tp
+
+
+def surface_distances(predictions: torch.Tensor, targets: torch.Tensor, threshold: float = 0.5,
+                      backend: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(d2_pt, d2_tp)``, int32 (B, H, W) each: at every boundary pixel of the prediction
+    (``p > threshold``) the squared distance to the nearest boundary pixel of the target (``t > 0``),
+    -1 elsewhere, and the mirror image; EDT_NONE where the opposite boundary is empty. CUDA tensors:
+    on their device, no host synchronisation. CPU tensors (and ``backend="host"``):
+    ``extract_boundaries`` + ``distance_transform_sq_np``, CPU tensors; the two agree exactly."""
+    if _use_device(backend, predictions, targets):
+        return _surface_device(predictions, targets, threshold)
+    d2_pt, d2_tp = _surface_host(predictions, targets, threshold)
+    return torch.from_numpy(d2_pt), torch.from_numpy(d2_tp)
+
+
+def _as_surface(a, b, threshold: float, backend: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(predictions, targets) -> their surface distances; a (d2_pt, d2_tp) pair passes through.
+    Both come back as (B, H * W)."""
+    _check_backend(backend)
+    if b is None:
+        if not isinstance(a, (tuple, list)) or len(a) != 2:
+            raise ValueError("need predictions and targets, or the pair surface_distances returns")
+        d2_pt, d2_tp = a
+    else:
+        d2_pt, d2_tp = surface_distances(a, b, threshold, backend)
+    if d2_pt.dtype != torch.int32 or d2_tp.dtype != torch.int32 or d2_pt.dim() < 2 or d2_pt.shape != d2_tp.shape \
+            or d2_pt.device != d2_tp.device:
+        raise ValueError(f"need two int32 tables of one shape (..., H, W) on one device, got {d2_pt.dtype} "
+                         f"{tuple(d2_pt.shape)} and {d2_tp.dtype} {tuple(d2_tp.shape)}")
+    H, W = d2_pt.shape[-2:]
+    return d2_pt.reshape(-1, H * W), d2_tp.reshape(-1, H * W)
+
+
+def _percentile_d2(d2: torch.Tensor, percentile: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(n, d2_(k)) of a (B, npx) table: the number of boundary pixels and their k-th smallest squared
+    distance, k = (percentile n + 99) // 100 (nearest rank), int64; the second is meaningless where
+    n = 0. The -1 entries sort first, so rank k sits at npx - n + k - 1."""
+    n = (d2 >= 0).sum(dim=1)
+    k = (percentile * n + 99) // 100
+    idx = (d2.shape[1] - n + k - 1).clamp(0, d2.shape[1] - 1)
+    return n, torch.sort(d2, dim=1)[0].gather(1, idx[:, None])[:, 0].to(torch.int64)
+
+
+def _sqrt_f64(x: torch.Tensor) -> torch.Tensor:
+    """Correctly rounded float64 square root of a non-negative integer tensor on its device (the CPU
+    kernel of torch.sqrt may be an ulp off, numpy's is not; the GPU one is correctly rounded)."""
+    x = x.to(torch.float64)
+    return x.sqrt() if x.is_cuda else torch.from_numpy(np.sqrt(x.numpy()))
+
+
+def compute_hausdorff_percentile_batch(predictions, targets=None, percentile: int = 95, threshold: float = 0.5,
+                                       backend: str = "auto") -> torch.Tensor:
+    """Per-sample ``percentile``-th percentile Hausdorff distance of the boundaries (HD95 by default),
+    float64 on the tables' device: per direction the nearest-rank percentile of the boundary pixels'
+    distances to the other boundary, the larger of the two directions; the square root of an exact
+    integer, and the Hausdorff distance at ``percentile=100``. inf when either boundary is empty.
+    Takes (predictions, targets) or the pair ``surface_distances`` returns."""
+    percentile = _check_percentile(percentile)
+    d2_pt, d2_tp = _as_surface(predictions, targets, threshold, backend)
+    n_p, k_p = _percentile_d2(d2_pt, percentile)
+    n_t, k_t = _percentile_d2(d2_tp, percentile)
+    h = _sqrt_f64(torch.maximum(k_p, k_t).clamp_min(0))  # (-1 where a boundary is empty: inf below)
+    return torch.where((n_p == 0) | (n_t == 0), torch.full_like(h, float("inf")), h)
+
+
+def compute_assd_batch(predictions, targets=None, threshold: float = 0.5, backend: str = "auto") -> torch.Tensor:
+    """Per-sample average symmetric surface distance, float64 on the tables' device: the mean over
+    the boundary pixels of both boundaries of the distance to the other boundary. inf when either
+    boundary is empty. Takes (predictions, targets) or the pair ``surface_distances`` returns."""
+    d2_pt, d2_tp = _as_surface(predictions, targets, threshold, backend)
+
+    def total(d2):
+        return _sqrt_f64(d2.clamp_min(0)).sum(dim=1), (d2 >= 0).sum(dim=1)  # the -1 entries add 0
+    s_p, n_p = total(d2_pt)
+    s_t, n_t = total(d2_tp)
+    assd = (s_p + s_t) / (n_p + n_t).clamp_min(1).to(torch.float64)
+    return torch.where((n_p == 0) | (n_t == 0), torch.full_like(assd, float("inf")), assd)
+
+
+def compute_surface_dice_batch(predictions, targets=None, tolerance: int = 2, smooth: float = 1e-6,
+                               threshold: float = 0.5, backend: str = "auto") -> torch.Tensor:
+    """Per-sample surface Dice at ``tolerance`` pixels, float64 on the tables' device:
+    (m_p + m_t + smooth) / (n_p + n_t + smooth) with n the boundary sizes and m the boundary pixels
+    within ``tolerance`` of the other boundary. Takes (predictions, targets) or the pair
+    ``surface_distances`` returns."""
+    tol2 = _check_surface_tolerance(tolerance) ** 2
+    d2_pt, d2_tp = _as_surface(predictions, targets, threshold, backend)
+    n = (d2_pt >= 0).sum(dim=1) + (d2_tp >= 0).sum(dim=1)
+    m = ((d2_pt >= 0) & (d2_pt <= tol2)).sum(dim=1) + ((d2_tp >= 0) & (d2_tp <= tol2)).sum(dim=1)
+    return (m.to(torch.float64) + smooth) / (n.to(torch.float64) + smooth)
+
+
 _probability_table_of_batch = probability_table  # evaluate_model has a parameter of that name
 # the per-image arrays evaluate_model(probability_metrics=True) adds, in this order
 PROBABILITY_METRIC_KEYS = ("auroc_scores", "average_precision_scores", "ece_scores", "brier_scores",
@@ -706,8 +914,9 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
                    calibration_bins: int = 16, probability_backend: str = "auto",
                    probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
                    tta_tile: int = 512, tta_overlap: int = 64, refine=None, physics_metrics: bool = False,
-                   physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05
-                   ) -> Dict[str, np.ndarray]:
+                   physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05,
+                   surface_metrics: bool = False, surface_percentile: int = 95, surface_tolerance: int = 2,
+                   surface_backend: str = "auto") -> Dict[str, np.ndarray]:
     """Per-image Dice / IoU (fused counters on the GPU) and boundary F1 / Hausdorff over a loader
     (src/evaluate.py:279-350). The boundary metrics of a CUDA batch come from one
     ``boundary_counts`` call and one device->host copy per batch (``boundary_backend``: "auto",
@@ -726,11 +935,19 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     ``physics_metrics=True`` adds ``rd_residuals`` (per-image mean squared reaction-diffusion
     residual, with ``physics_D`` and ``physics_a``), ``pf_energies`` (per-image mean phase-field
     energy density, ``physics_eps``) and ``interface_fractions`` (the share of pixels with
-    0.1 < u < 0.9) from one ``pde.energies`` call and one device->host copy per batch."""
+    0.1 < u < 0.9) from one ``pde.energies`` call and one device->host copy per batch.
+    ``surface_metrics=True`` adds ``hausdorff_percentile_distances`` (``surface_percentile``: 95 is
+    HD95; NaN where a boundary is empty, as ``hausdorff_distances``), ``assd_distances`` (likewise) and
+    ``surface_dice_scores`` (at ``surface_tolerance`` pixels) from one ``surface_distances`` call
+    (``surface_backend``) and one device->host copy per batch."""
     predictor = None
     _check_refine(refine)  # both refused before any GPU work
     if physics_metrics:
         _check_physics(physics_D, physics_a, physics_eps)
+    if surface_metrics:
+        surface_percentile = _check_percentile(surface_percentile)
+        surface_tolerance = _check_surface_tolerance(surface_tolerance)
+        _check_backend(surface_backend)
     if refine is not None or physics_metrics:
         from .pde import energies as _energies, evolve as _evolve
     if tta is not None:  # refused before any GPU work
@@ -749,6 +966,7 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
     of1, aji, cerr = [], [], []
     prob = [[] for _ in range(6)]
     phys = [[] for _ in range(3)]
+    surf = [[] for _ in range(3)]
     for images, masks in dataloader:
         images, masks = images.to(device, non_blocking=True), masks.to(device, non_blocking=True)
         outputs = model(images) if predictor is None else predictor.predict_batch(images)[0]
@@ -794,6 +1012,14 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
             three = torch.stack([e[:, 0], e[:, 1], n.to(torch.float64) / px]).cpu().numpy()
             for acc, row in zip(phys, three):
                 acc.extend(row.tolist())
+        if surface_metrics:
+            pair = surface_distances(outputs, masks, threshold, surface_backend)
+            three = torch.stack([compute_hausdorff_percentile_batch(pair, percentile=surface_percentile),
+                                 compute_assd_batch(pair),
+                                 compute_surface_dice_batch(pair, tolerance=surface_tolerance)]).cpu().numpy()
+            three[:2] = np.where(np.isfinite(three[:2]), three[:2], np.nan)
+            for acc, row in zip(surf, three):
+                acc.extend(row.tolist())
     out = {"dice_scores": np.array(dice), "iou_scores": np.array(iou)}
     if boundary_metrics:
         out["boundary_f1_scores"] = np.array(bf1)
@@ -807,6 +1033,9 @@ def evaluate_model(model, dataloader, device, threshold: float = 0.5, boundary_m
             out[key] = np.array(acc, dtype=np.float64)
     if physics_metrics:
         for key, acc in zip(PHYSICS_METRIC_KEYS, phys):
+            out[key] = np.array(acc, dtype=np.float64)
+    if surface_metrics:
+        for key, acc in zip(SURFACE_METRIC_KEYS, surf):
             out[key] = np.array(acc, dtype=np.float64)
     return out
 
@@ -869,7 +1098,8 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
                          calibration_bins: int = 16,
                          probability_table: Optional[ProbabilityTable] = None, tta: Optional[str] = None,
                          tta_tile: int = 512, tta_overlap: int = 64, refine=None, physics_metrics: bool = False,
-                         physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05
+                         physics_D: float = 1.0, physics_a: float = 0.5, physics_eps: float = 0.05,
+                         surface_metrics: bool = False, surface_percentile: int = 95, surface_tolerance: int = 2
                          ) -> Dict[str, np.ndarray]:
     """Per-image metrics of ``model`` on a COCO-annotated test folder (src/evaluate.py:476-522).
     ``device_cache=True`` serves the (bit-identical) batches from a device-resident cache
@@ -879,7 +1109,9 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
     a ``ProbabilityTable`` passed as ``probability_table`` receives the pooled table of the set).
     ``tta``, ``tta_tile``, ``tta_overlap``: test-time augmentation, as ``evaluate_model``.
     ``refine``, ``physics_metrics``, ``physics_D``, ``physics_a``, ``physics_eps``: PDE refinement
-    of the probabilities and the per-image physics arrays, as ``evaluate_model``."""
+    of the probabilities and the per-image physics arrays, as ``evaluate_model``.
+    ``surface_metrics``, ``surface_percentile``, ``surface_tolerance``: the percentile Hausdorff
+    distance, ASSD and surface Dice arrays, as ``evaluate_model``."""
     if probability_metrics:
         _check_calibration_bins(calibration_bins)
     _check_refine(refine)
@@ -889,6 +1121,9 @@ def evaluate_on_test_set(model, test_dir, test_json, device, batch_size: int = 8
     if physics_metrics:
         _check_physics(physics_D, physics_a, physics_eps)
         tta_kw.update(physics_metrics=True, physics_D=physics_D, physics_a=physics_a, physics_eps=physics_eps)
+    if surface_metrics:
+        tta_kw.update(surface_metrics=True, surface_percentile=_check_percentile(surface_percentile),
+                      surface_tolerance=_check_surface_tolerance(surface_tolerance))
     from torch.utils.data import DataLoader
 
     from .dataset import CellSegmentationDataset, DeviceCachedLoader
@@ -922,4 +1157,6 @@ __all__ = ["compute_iou", "compute_iou_batch", "extract_boundaries", "compute_bo
            "format_metric_report", "evaluate_on_test_set", "object_counts", "label_components",
            "compute_object_f1_batch", "compute_aji_batch", "probability_table", "threshold_sweep_counts",
            "compute_auroc_batch", "compute_average_precision_batch", "compute_ece_batch", "compute_brier_batch",
-           "best_threshold_batch", "ProbabilityTable", "PHYSICS_METRIC_KEYS"]
+           "best_threshold_batch", "ProbabilityTable", "PHYSICS_METRIC_KEYS", "EDT_NONE", "SURFACE_METRIC_KEYS",
+           "distance_transform_sq_np", "distance_transform_sq", "surface_distances",
+           "compute_hausdorff_percentile_batch", "compute_assd_batch", "compute_surface_dice_batch"]

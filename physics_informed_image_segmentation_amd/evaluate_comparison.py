@@ -19,8 +19,8 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from .evaluate import (PHYSICS_METRIC_KEYS, PROBABILITY_METRIC_KEYS, ProbabilityTable, compare_models_statistically,
-                       compute_statistics, evaluate_on_test_set, format_metric_report)
+from .evaluate import (PHYSICS_METRIC_KEYS, PROBABILITY_METRIC_KEYS, SURFACE_METRIC_KEYS, ProbabilityTable,
+                       compare_models_statistically, compute_statistics, evaluate_on_test_set, format_metric_report)
 from .unet import UNet
 
 METRIC_KEYS = ("dice_scores", "iou_scores", "boundary_f1_scores", "hausdorff_distances")
@@ -33,7 +33,10 @@ _COLUMNS = {"dice_scores": "dice", "iou_scores": "iou", "boundary_f1_scores": "b
             "average_precision_scores": "average_precision", "ece_scores": "ece", "brier_scores": "brier",
             "best_threshold_dice_scores": "best_threshold_dice", "best_thresholds": "best_threshold",
             # PHYSICS_METRIC_KEYS (evaluate.py), only with the physics metrics switched on
-            "rd_residuals": "rd_residual", "pf_energies": "pf_energy", "interface_fractions": "interface_fraction"}
+            "rd_residuals": "rd_residual", "pf_energies": "pf_energy", "interface_fractions": "interface_fraction",
+            # SURFACE_METRIC_KEYS (evaluate.py), only with the surface metrics switched on
+            "hausdorff_percentile_distances": "hausdorff_percentile", "assd_distances": "assd",
+            "surface_dice_scores": "surface_dice"}
 _DEFAULT_OUT = Path(__file__).resolve().parent.parent / "output"
 
 
@@ -89,7 +92,8 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
                          probability_metrics: bool = False, calibration_bins: int = 16,
                          tta: Optional[str] = None, tta_tile: int = 512, tta_overlap: int = 64, refine=None,
                          physics_metrics: bool = False, physics_D: float = 1.0, physics_a: float = 0.5,
-                         physics_eps: float = 0.05) -> Dict:
+                         physics_eps: float = 0.05, surface_metrics: bool = False, surface_percentile: int = 95,
+                         surface_tolerance: int = 2) -> Dict:
     """``probability_metrics=True`` adds the six probability-level columns and rows and writes, per
     model, threshold_sweep_<model>_<ts>.csv (the pooled curves, 1024 rows) and
     reliability_<model>_<ts>.csv (``calibration_bins`` rows); the pooled best thresholds go into
@@ -97,7 +101,9 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
     models under test-time augmentation (``evaluate_model``); files and columns do not change.
     ``refine`` (a ``pde.PDERefine``) evolves both models' probabilities under the PDE before every
     metric; ``physics_metrics=True`` adds the three physics columns and rows (``rd_residual``,
-    ``pf_energy``, ``interface_fraction``), computed with ``physics_D``, ``physics_a``, ``physics_eps``."""
+    ``pf_energy``, ``interface_fraction``), computed with ``physics_D``, ``physics_a``, ``physics_eps``.
+    ``surface_metrics=True`` adds the three surface-distance columns and rows (``hausdorff_percentile`` at
+    ``surface_percentile``, ``assd``, ``surface_dice`` at ``surface_tolerance`` pixels)."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -108,6 +114,8 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
         obj["refine"] = refine
     if physics_metrics:
         obj.update(physics_metrics=True, physics_D=physics_D, physics_a=physics_a, physics_eps=physics_eps)
+    if surface_metrics:
+        obj.update(surface_metrics=True, surface_percentile=surface_percentile, surface_tolerance=surface_tolerance)
     pooled = {"baseline": ProbabilityTable(), "pde": ProbabilityTable()} if probability_metrics else {}
     prob = {tag: dict(probability_metrics=True, calibration_bins=calibration_bins, probability_table=tab)
             for tag, tab in pooled.items()}
@@ -127,7 +135,8 @@ def evaluate_and_compare(baseline_model_path: Path, pde_model_path: Path, test_d
     per_image = {"image_id": range(len(base["dice_scores"]))}
     for key in (METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
                 + (PROBABILITY_METRIC_KEYS if probability_metrics else ())
-                + (PHYSICS_METRIC_KEYS if physics_metrics else ())):
+                + (PHYSICS_METRIC_KEYS if physics_metrics else ())
+                + (SURFACE_METRIC_KEYS if surface_metrics else ())):
         col = _COLUMNS[key]
         per_image[f"baseline_{col}"] = base[key]
         per_image[f"pde_{col}"] = pde[key]
@@ -176,10 +185,11 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
                              probability_metrics: bool = False, calibration_bins: int = 16,
                              tta: Optional[str] = None, tta_tile: int = 512, tta_overlap: int = 64, refine=None,
                          physics_metrics: bool = False, physics_D: float = 1.0, physics_a: float = 0.5,
-                         physics_eps: float = 0.05) -> Dict:
+                         physics_eps: float = 0.05, surface_metrics: bool = False, surface_percentile: int = 95,
+                         surface_tolerance: int = 2) -> Dict:
     """``probability_metrics=True`` adds the six per-image probability-level arrays to the pooled
     statistics (the per-model sweep and reliability files belong to ``evaluate_and_compare``).
-    ``tta``, ``refine`` and the physics metrics as ``evaluate_and_compare``."""
+    ``tta``, ``refine``, the physics metrics and the surface metrics as ``evaluate_and_compare``."""
     import pandas as pd
     out_dir = Path(output_dir) if output_dir is not None else _DEFAULT_OUT
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -192,9 +202,12 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
         obj["refine"] = refine
     if physics_metrics:
         obj.update(physics_metrics=True, physics_D=physics_D, physics_a=physics_a, physics_eps=physics_eps)
+    if surface_metrics:
+        obj.update(surface_metrics=True, surface_percentile=surface_percentile, surface_tolerance=surface_tolerance)
     metric_keys = (METRIC_KEYS + (OBJECT_METRIC_KEYS if object_metrics else ())
                    + (PROBABILITY_METRIC_KEYS if probability_metrics else ())
-                   + (PHYSICS_METRIC_KEYS if physics_metrics else ()))
+                   + (PHYSICS_METRIC_KEYS if physics_metrics else ())
+                   + (SURFACE_METRIC_KEYS if surface_metrics else ()))
     print("=" * 70 + "\nREPEATED EXPERIMENTS EVALUATION\n" + "=" * 70)
     print(f"Number of runs: {len(baseline_model_paths)}")
     pooled = {"baseline": {k: [] for k in metric_keys}, "pde": {k: [] for k in metric_keys}}
@@ -230,5 +243,5 @@ def run_repeated_evaluations(baseline_model_paths: List[Path], pde_model_paths: 
     return {"baseline_metrics": base, "pde_metrics": pde, "comparison_results": cmp, "aggregated_csv": aggregated_csv}
 
 
-__all__ = ["METRIC_KEYS", "OBJECT_METRIC_KEYS", "PROBABILITY_METRIC_KEYS", "PHYSICS_METRIC_KEYS",
+__all__ = ["METRIC_KEYS", "OBJECT_METRIC_KEYS", "PROBABILITY_METRIC_KEYS", "PHYSICS_METRIC_KEYS", "SURFACE_METRIC_KEYS",
            "make_json_serializable", "load_model", "evaluate_and_compare", "run_repeated_evaluations"]
