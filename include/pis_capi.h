@@ -264,7 +264,15 @@ int pis_version(void);
                                  boundaries at 8 x 512^2 (the rule, fixed before measuring), 150.4 us against 156.3
                                  (1) and 158.3 (0); one set pixel in a corner of 2048^2 takes 421.9 / 458.2 /
                                  3247.5 us (tools/bench_surface.py, profiles/surface_metrics.txt) */
-#define PIS_TUNE_NKEYS 56
+#define PIS_TUNE_CONVT_WGRAD_TILE 56 /* pis_convt2x2_wgrad (csrc/wgrad.hip): 1 (default) the fp16x3 kernel on 256 x 128
+                                 block tiles (256 columns (i, j, o) of dy x 128 input channels; a K-step of 32
+                                 pixels is staged once per tile, about 512 blocks, chains of 512 .. 8192 pixels)
+                                 where key 13 = 4, W % 32 == 0, Cin % 128 == 0, (4 Cout) % 256 == 0, the strides
+                                 are multiples of 4 and the operands 16-B aligned; 0: the 128 x 128 row-staged
+                                 kernel (Cin >= 256) and the column-staged bf16x6 kernel, as every other shape.
+                                 The key may change between any two calls: pis_convt2x2_wgrad_ws is the maximum
+                                 over every plan */
+#define PIS_TUNE_NKEYS 57
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -434,6 +442,9 @@ size_t pis_convt2x2_wgrad_ws(int B, int H, int W, int Cin, int Cout);
 int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw_ijoc,
                        float* db, int B, int H, int W, int Cin, int Cout, int flags, void* ws,
                        size_t ws_bytes, pis_stream_t stream);
+/* Tooling and tests: the number of split-K slabs of the 256 x 128 tile plan (PIS_TUNE_CONVT_WGRAD_TILE) at this
+ * shape, 0 where the shape is outside that kernel's contract. */
+int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout);
 
 /* ---- 2x2 max pooling (src/unet.py:126,181-186) ----
  * H, W are the INPUT resolution. y is contiguous (ld = C).

@@ -24,6 +24,7 @@ PIS_TUNE_DIRECT_MFMA16 = 53  # include/pis_capi.h: MFMA shape of the direct fp16
 PIS_TUNE_PROB_VARIANT = 52 # include/pis_capi.h: pis_probability_table kernel form (tools/bench_probability.py)
 PIS_TUNE_EVOLVE_T = 54  # include/pis_capi.h: steps per launch of pis_pde_evolve (1, 2, 4 or 8)
 PIS_TUNE_EDT_PRUNE = 55  # include/pis_capi.h: what the distance transform's outward search skips (0, 1 or 3)
+PIS_TUNE_CONVT_WGRAD_TILE = 56  # include/pis_capi.h: transposed-conv weight gradient on 256 x 128 tiles (1) or the older kernels (0)
 PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
@@ -82,6 +83,7 @@ _SIGNATURES = {
     "pis_convt2x2_dgrad": ([P, I, P, P, I, P, I, I, I, I, I, I, I, P], c_int),
     "pis_convt2x2_wgrad_ws": ([I, I, I, I, I], c_size_t),
     "pis_convt2x2_wgrad": ([P, I, P, I, P, P, I, I, I, I, I, I, P, Z, P], c_int),
+    "pis_debug_convt2x2_wgrad_tile_splits": ([I, I, I, I, I], c_int),
     "pis_maxpool2x2_fwd": ([P, I, P, I, I, I, I, P], c_int),
     "pis_maxpool2x2_bwd": ([P, I, P, P, I, P, I, I, I, I, I, P], c_int),
     "pis_head_fwd": ([P, I, P, P, P, P, L, I, P], c_int),

@@ -1287,6 +1287,204 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   }
 }
 
+// The transposed-conv weight gradient on 256 x 128 tiles (pis_tune key 56): wgrad_h3t_kernel<UP2>'s
+// contraction, fp16x3 with one power-of-two scale per operand and K-step, on a block tile of 256
+// columns of A (for 128 -> 64 channels all four taps x 64 output channels: one block owns the whole
+// dW) x 128 input channels, so a K-step's 32 pixels of x are staged once per 256 columns of A and
+// its dy rows once per 128 input channels, and 512 blocks (one resident generation at two per CU)
+// already give chains of 512 .. 1024 pixels at the training shapes (67 MB of slabs per layer; the
+// 128 x 128 form writes twice that at 256 -> 128 and 512 -> 256 channels). DESIGN §4 round 10.
+// Wave (wm, wn): columns 128 wm .. of A x input channels 64 wn ..: 4 x 2 accumulator blocks of
+// 32 x 32 (128 registers), 24 transposed fragment reads per 48 MFMAs.
+// LDS: ONE K-step, six planes of wgrad_h3t_kernel's [32 pixels][128 columns] layout (wtsw): A hi
+// (columns 0..127, 128..255), A lo (the same), B hi, B lo = 48 KB, two blocks per CU. The raw
+// operands of K-step st + 1 are loaded while K-step st multiplies (one register set) and are split
+// into the planes between the K-step's second barrier and the next one's first; the CU's other
+// block multiplies meanwhile.
+// Needs W % 32 == 0 and pix_per_split % 32 == 0 (every split is whole K-steps of one image row),
+// Mp % 256 == 0, Np % 128 == 0, Ca % 4 == 0, lda / ldb % 4 == 0 and 16-B aligned operands.
+constexpr int WU_BM = 256, WU_BN = 128;
+constexpr int WU_LDS = 6 * WT_PLANE;  // fp16 elements
+
+__global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
+  __shared__ __attribute__((aligned(16))) _Float16 smem[WU_LDS];
+  __shared__ float red[2][2][4];  // [K-step parity][A|B][wave] maxima
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1, li = lane & 31, lh = lane >> 5;
+  const int ntn = g.Np / WU_BN;
+  const int tiles = (g.Mp / WU_BM) * ntn;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int split = bid / tiles;
+  const int tile = bid - split * tiles;
+  const int m0 = (tile / ntn) * WU_BM, n0 = (tile % ntn) * WU_BN;
+  const int p_begin = split * g.pix_per_split;
+  const int p_end = min(g.P, p_begin + g.pix_per_split);
+  const int nst = max(0, (p_end - p_begin) / WT_BK);
+  // staging: pixel rows srow + 8 j, float4 column sc4 of B and of each 128-column half of A
+  const int srow = tid >> 5, sc4 = tid & 31;
+  const float* gb = g.b + n0 + 4 * sc4;
+  const float* ga[2];  // this thread's column group of half h at dy pixel (i, j) of the image's first 2 x 2 block
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int col = m0 + 128 * h + 4 * sc4, ij = col / g.Ca;
+    ga[h] = g.a + (col - ij * g.Ca) + ((size_t)(ij >> 1) * (2 * g.W) + (ij & 1)) * g.lda;
+  }
+  const bool do_bias = g.part_bias != nullptr && n0 == 0;
+  f32x4 bsum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+
+  f32x4 xa[2][4], xb[4];
+  auto gload = [&](int st) __attribute__((always_inline)) {
+    // the K-step's 32 pixels: image row (b, y), columns x0 .. x0 + 31; A rows two dy pixels apart
+    const int p0 = p_begin + st * WT_BK;
+    const int hw = g.H * g.W, b = p0 / hw, rem = p0 - b * hw, y = rem / g.W, x0 = rem - y * g.W;
+    const size_t abase = (((size_t)b * 2 * g.H + 2 * y) * (2 * g.W) + 2 * x0) * g.lda;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = srow + 8 * j;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) xa[h][j] = *reinterpret_cast<const f32x4*>(ga[h] + abase + (size_t)(2 * r) * g.lda);
+      xb[j] = *reinterpret_cast<const f32x4*>(gb + (size_t)(p0 + r) * g.ldb);
+    }
+  };
+  auto publish = [&](int par) __attribute__((always_inline)) {
+    if (do_bias) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bsum[0] += xa[0][j];
+        bsum[1] += xa[1][j];
+      }
+    }
+    const float ma = wave_max_nonneg(absmax_x4(xa));
+    const float mb = wave_max_nonneg(absmax_x4(xb));
+    if (lane == 0) {
+      red[par][0][wave] = ma;
+      red[par][1][wave] = mb;
+    }
+  };
+  float sa = 0.f, sb = 0.f, sa_min = __builtin_inff(), sb_min = __builtin_inff();  // the staged K-step's scales
+  auto split_store = [&](int par) __attribute__((always_inline)) {
+    auto umax4 = [](const float (&r)[4]) __attribute__((always_inline)) {  // r >= 0: bit-pattern max
+      return __uint_as_float(max(max(__float_as_uint(r[0]), __float_as_uint(r[1])),
+                                 max(__float_as_uint(r[2]), __float_as_uint(r[3]))));
+    };
+    sa = h3_keep(sa, umax4(red[par][0]), sa_min);
+    sb = h3_keep(sb, umax4(red[par][1]), sb_min);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int off = wtsw(srow + 8 * j, sc4 >> 1) + 4 * (sc4 & 1);
+      u32x2 h, l;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        split2h_x4(xa[hf][j] * sa, h, l);
+        *reinterpret_cast<u32x2*>(smem + hf * WT_PLANE + off) = h;
+        *reinterpret_cast<u32x2*>(smem + (2 + hf) * WT_PLANE + off) = l;
+      }
+      split2h_x4(xb[j] * sb, h, l);
+      *reinterpret_cast<u32x2*>(smem + 4 * WT_PLANE + off) = h;
+      *reinterpret_cast<u32x2*>(smem + 5 * WT_PLANE + off) = l;
+    }
+  };
+
+  // transposed-read lane roles, as wgrad_h3t_kernel
+  const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const int kh = gq >> 1, chk = 2 * (gq & 1) + (pp >> 1), slot = 4 * (pp & 1);
+  auto frag = [&](const _Float16* plane, int ks, int col0) __attribute__((always_inline)) {
+    const int row = 16 * ks + 8 * kh + q, ch = col0 / 8 + chk;
+    const s16x4 lo4 = tr_read(plane + wtsw(row, ch) + slot);
+    const s16x4 hi4 = tr_read(plane + wtsw(row + 4, ch) + slot);
+    return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+  };
+  const _Float16* a_hi = smem + wm * WT_PLANE;
+  const _Float16* a_lo = smem + (2 + wm) * WT_PLANE;
+  const _Float16* b_hi = smem + 4 * WT_PLANE;
+  const _Float16* b_lo = smem + 5 * WT_PLANE;
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  // the partial sums are in units ua * ub, kept as two factors (0: none yet), as wgrad_h3t_kernel
+  float ua = 0.f, ub = 0.f;
+
+  if (nst > 0) {
+    gload(0);
+    publish(0);
+    __syncthreads();
+    split_store(0);
+    if (nst > 1) gload(1);
+  }
+#pragma unroll 1
+  for (int st = 0; st < nst; ++st) {
+    __syncthreads();  // K-step st staged
+    if (sa != ua || sb != ub) {  // the partial sums in this K-step's units (exact: powers of two)
+      if (ua != 0.f) {
+        const float fa = sa / ua, fb = sb / ub;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc[a][b] = (acc[a][b] * fa) * fb;
+      }
+      ua = sa;
+      ub = sb;
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      f16x8 bf[2][2];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        bf[0][b] = frag(b_hi, ks, 64 * wn + 32 * b);
+        bf[1][b] = frag(b_lo, ks, 64 * wn + 32 * b);
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const f16x8 ah = frag(a_hi, ks, 32 * a), al = frag(a_lo, ks, 32 * a);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf[0][b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf[1][b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf[0][b], acc[a][b], 0, 0, 0);
+        }
+      }
+    }
+    const bool more = st + 1 < nst;
+    if (more) publish((st + 1) & 1);
+    __syncthreads();  // every wave has read K-step st's fragments
+    if (more) {
+      split_store((st + 1) & 1);
+      if (st + 2 < nst) gload(st + 2);
+    }
+  }
+  float* out = g.part + (size_t)split * g.Mp * g.Np;
+  const float inv_a = ua != 0.f ? 1.f / ua : 0.f, inv_b = ub != 0.f ? 1.f / ub : 0.f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int n = n0 + 64 * wn + 32 * b + li;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + 128 * wm + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        out[(size_t)m * g.Np + n] = (acc[a][b][r] * inv_a) * inv_b;
+      }
+    }
+  if (do_bias) {  // column sums over the block's pixels: the 8 threads of each column group, fixed order
+    f32x4* rb4 = reinterpret_cast<f32x4*>(smem);  // the loop's last barrier is behind every fragment read
+    rb4[tid] = bsum[0];
+    rb4[256 + tid] = bsum[1];
+    __syncthreads();
+    if (tid < 64) {
+      const int base = 256 * (tid >> 5) + (tid & 31);
+      f32x4 t = rb4[base];
+#pragma unroll
+      for (int r = 1; r < 8; ++r) t += rb4[base + 32 * r];
+      *reinterpret_cast<f32x4*>(g.part_bias + (size_t)split * g.Mp + m0 + 4 * tid) = t;
+    }
+  }
+}
+
 // wgrad_h3t_kernel's EX form: whole K-steps in every split (pix_per_split is a multiple of 32) and
 // 31-bit row offsets for the buffer loads (the batch offsets go into the base pointers)
 static bool h3t_exact(const WgradArgs& a) {
@@ -1666,10 +1864,45 @@ static bool convt_wgrad_t_ok(int B, int H, int W, int Cin, int Cout, int ldx, in
          plan_wgrad(4 * Cout, Cin, B * H * W, 4 * Cout, Cin).pps % WT_BK == 0;
 }
 
+// key 56: the 256 x 128 tile kernel (wgrad_up2_tile_kernel). One resident generation, tiles x splits
+// about 512 blocks (two per CU); pps a multiple of the K-step, chains of 512 .. 8192 pixels
+static bool convt_wgrad_tile_shape(int W, int Cin, int Cout) {
+  return W % WT_BK == 0 && Cin % WU_BN == 0 && (4 * Cout) % WU_BM == 0;
+}
+
+static WgradPlan plan_convt_tile(int Mp, int Np, int P) {
+  WgradPlan p{};
+  p.bm = WU_BM;
+  p.bn = WU_BN;
+  const int tiles = (Mp / WU_BM) * (Np / WU_BN);
+  const int64_t want_splits = std::max<int64_t>(1, cdiv(512, tiles));
+  int64_t pps = std::min<int64_t>(std::max<int64_t>(512, cdiv(P, want_splits)), 8192);
+  pps = cdiv(pps, WT_BK) * WT_BK;
+  p.pps = (int)pps;
+  p.splits = (int)cdiv(P, pps);
+  p.part_bytes = (size_t)p.splits * Mp * Np * sizeof(float);
+  p.bias_bytes = (size_t)p.splits * Mp * sizeof(float);
+  return p;
+}
+
+static bool convt_wgrad_tile_ok(int W, int Cin, int Cout, int ldx, int lddy, const void* x, const void* dy) {
+  return tune_get(PIS_TUNE_CONVT_WGRAD_TILE) != 0 && tune_get(PIS_TUNE_CONVT_GEMM) == 4 &&
+         convt_wgrad_tile_shape(W, Cin, Cout) && ldx % 4 == 0 && lddy % 4 == 0 && ((uintptr_t)x & 15) == 0 &&
+         ((uintptr_t)dy & 15) == 0;
+}
+
 extern "C" size_t pis_convt2x2_wgrad_ws(int B, int H, int W, int Cin, int Cout) {
-  // either plan (key 13 may change after the workspace is sized)
-  return std::max(wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, Cout, Cin)),
-                  wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, 4 * Cout, Cin)));
+  // the maximum over every plan (keys 13 and 56 may change after the workspace is sized)
+  size_t n = std::max(wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, Cout, Cin)),
+                      wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, 4 * Cout, Cin)));
+  if (convt_wgrad_tile_shape(W, Cin, Cout)) n = std::max(n, wgrad_ws_bytes(plan_convt_tile(4 * Cout, Cin, B * H * W)));
+  return n;
+}
+
+// tooling and tests: the splits of the 256 x 128 tile plan (0 where the shape is outside its contract)
+extern "C" int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !convt_wgrad_tile_shape(W, Cin, Cout)) return 0;
+  return plan_convt_tile(4 * Cout, Cin, B * H * W).splits;
 }
 
 extern "C" int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw_ijoc,
@@ -1684,6 +1917,21 @@ extern "C" int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int 
   hipStream_t s = (hipStream_t)stream;
   const int acc = flags & PIS_ACCUMULATE;
   const int P = B * H * W;
+  if (convt_wgrad_tile_ok(W, Cin, Cout, ldx, lddy, x, dy)) {
+    const WgradPlan pl = plan_convt_tile(4 * Cout, Cin, P);
+    WgradArgs a{};
+    a.a = dy; a.lda = lddy; a.a_up2 = 1; a.Ca = Cout;
+    a.b = x; a.ldb = ldx; a.b_mode = B_PLAIN; a.Cb = Cin;
+    a.B = B; a.H = H; a.W = W; a.P = P; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
+    a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
+    a.pix_per_split = pl.pps;
+    const int tiles = (a.Mp / WU_BM) * (a.Np / WU_BN);
+    hipLaunchKernelGGL(wgrad_up2_tile_kernel, dim3(tiles * pl.splits), dim3(256), 0, s, a);
+    int rc = launch_status("wgrad_up2_tile");
+    if (!rc) rc = reduce_slabs2(a.part, pl.splits, (int64_t)a.Mp * a.Np, dw_ijoc, a.part_bias, pl.splits * 4, Cout, db,
+                                acc, s);
+    return rc;
+  }
   if (convt_wgrad_t_ok(B, H, W, Cin, Cout, ldx, lddy, x, dy)) {
     const WgradPlan pl = plan_wgrad(4 * Cout, Cin, P, 4 * Cout, Cin);  // 128 x 128 tiles (taps may share one)
     WgradArgs a{};

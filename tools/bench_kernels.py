@@ -10,6 +10,10 @@ process (cdna_hip_programming.md §5.4 rule 24). Prints TFLOP/s per layer.
 the original weights), e.g. --key 51 --variants 0,1 --ops dgrad,pdgrad for the overlap-add input
 gradient against the V(dz) form: under rocprofv3 --kernel-trace a layer's dz pass, GEMM and output
 transform per variant.
+
+--convt: the four transposed convs instead, e.g. --convt --key 56 --variants 0,1 --ops wgrad for the
+weight gradient on 256 x 128 tiles (1) against the older kernels (0); each figure is the minimum of
+the rounds with their spread beside it.
 """
 import argparse
 import os
@@ -137,7 +141,7 @@ def main():
 
 
 def bench_convt(lib, args, variants, default, s, dev, opsel):
-    for name, H, cin, cout in UP_LAYERS:
+    for name, H, cin, cout in [l for l in UP_LAYERS if not args.layers or l[0] in args.layers.split(",")]:
         x = torch.rand(B, H, H, cin, device=dev)
         dy = torch.randn(B, 2 * H, 2 * H, cout, device=dev)
         w = torch.randn(2, 2, cout, cin, device=dev) * 0.05
@@ -168,9 +172,9 @@ def bench_convt(lib, args, variants, default, s, dev, opsel):
         lib.pis_tune(args.key, default)
         for op in opsel:
             line = f"{name:12s} {op:6s}"
-            for v in variants:
+            for v in variants:  # min of the rounds, and their spread (max - min)
                 ms = min(results[(op, v)])
-                line += f"  v{v}: {ms:7.3f} ms {flops / ms / 1e9:6.1f} TF/s"
+                line += f"  v{v}: {ms:7.3f} ms (+{max(results[(op, v)]) - ms:5.3f}) {flops / ms / 1e9:6.1f} TF/s"
             print(line, flush=True)
 
 
