@@ -83,7 +83,9 @@ int pis_version(void);
                                     ahead, epilogue through LDS (16-B pixel stores), and the weight gradient on the
                                     row-staged split-K kernel where Cin >= 256 (needs M, N % 128, w % 32; else 3);
                                     3 fp32-class fp16x3 on fp16 MFMA, K-step 16 (per-wave, per-K-step power-of-two
-                                    scales), 1 bf16x6 on bf16 MFMA, 2 on fp32 MFMA; 0 generic implicit GEMM */
+                                    scales), 1 bf16x6 on bf16 MFMA, 2 on fp32 MFMA; 0 generic implicit GEMM. The
+                                    contract of every arm, and the only code that reads the key: the planner,
+                                    csrc/convt_plan.h ("Transposed-conv arms") */
 #define PIS_TUNE_WGRAD_X6 14     /* Winograd and transposed-conv weight-gradient GEMMs: 3 (default) fp16x3 where the
                                     layer has >= 256 input channels, bf16x6 elsewhere; 1 fp32-accurate bf16x6 on
                                     bf16 MFMA everywhere, 2 fp16x3 (as key 10 = 4) everywhere (-1 % on the step: the
@@ -271,7 +273,8 @@ int pis_version(void);
                                  are multiples of 4 and the operands 16-B aligned; 0: the 128 x 128 row-staged
                                  kernel (Cin >= 256) and the column-staged bf16x6 kernel, as every other shape.
                                  The key may change between any two calls: pis_convt2x2_wgrad_ws is the maximum
-                                 over every plan */
+                                 over every plan. The contract and the only code that reads the key: the planner,
+                                 csrc/convt_plan.h ("Transposed-conv arms") */
 #define PIS_TUNE_NKEYS 57
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
@@ -437,7 +440,8 @@ int pis_convt2x2_prep(const float* w_ijoc, float* w_cijo, int Cin, int Cout, pis
 int pis_convt2x2_dgrad(const float* dy, int lddy, const float* w_cijo, const float* mask, int ldm,
                        float* dx, int lddx, int B, int H, int W, int Cin, int Cout, int flags,
                        pis_stream_t stream);
-/* wgrad: dw[i][j][o][c] (+)= sum_(h,w) dy[(2h+i,2w+j)][o] x[(h,w)][c]; db[o] (+)= sum dy[.][o] */
+/* wgrad: dw[i][j][o][c] (+)= sum_(h,w) dy[(2h+i,2w+j)][o] x[(h,w)][c]; db[o] (+)= sum dy[.][o]
+ * (Cin, Cout multiples of 64; the size query answers 0 outside that contract) */
 size_t pis_convt2x2_wgrad_ws(int B, int H, int W, int Cin, int Cout);
 int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw_ijoc,
                        float* db, int B, int H, int W, int Cin, int Cout, int flags, void* ws,
@@ -445,6 +449,16 @@ int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float
 /* Tooling and tests: the number of split-K slabs of the 256 x 128 tile plan (PIS_TUNE_CONVT_WGRAD_TILE) at this
  * shape, 0 where the shape is outside that kernel's contract. */
 int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout);
+/* Tooling and tests: the algorithm the planner (csrc/convt_plan.h) resolves for a call of this shape under the
+ * current keys. op 0: pis_convt2x2_fwd with ld_src = ldx, ld_dst = ldy and a bias; op 1: pis_convt2x2_dgrad with
+ * ld_src = lddy, ld_dst = lddx = ldm and PIS_MASK; op 2: pis_convt2x2_wgrad with ld_src = ldx, ld_dst = lddy.
+ * aligned16 != 0: every pointer of the call is 16-byte aligned; 0: none is. Launches nothing.
+ * op 0 / 1: 1 fp16x3 K-step 32, 2 / 3 / 4 the K-step-16 GEMM in fp16x3 / bf16x6 / fp32 MFMA, 5 implicit GEMM
+ * (ConvtAlgo). op 2: arm | (kernel + 1) << 4 | (bm / 64) << 8 | (bn / 64) << 12 with arm 1 the 256 x 128 tile
+ * kernel (kernel field 0), 2 the row-staged 128 x 128 kernel, 3 generic split-K (ConvtWgradAlgo), kernel 0 fp32
+ * MFMA, 1 bf16x6, 2 fp16x3 by columns, 3 fp16x3 by rows, 4 its whole-K-step form, 5 its timing twin
+ * (WgradKernel), bm x bn the block tile; 0 outside pis_convt2x2_wgrad's contract or for another op. */
+int pis_debug_convt2x2_algo(int op, int B, int H, int W, int Cin, int Cout, int ld_src, int ld_dst, int aligned16);
 
 /* ---- 2x2 max pooling (src/unet.py:126,181-186) ----
  * H, W are the INPUT resolution. y is contiguous (ld = C).

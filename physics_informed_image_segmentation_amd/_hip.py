@@ -84,6 +84,7 @@ _SIGNATURES = {
     "pis_convt2x2_wgrad_ws": ([I, I, I, I, I], c_size_t),
     "pis_convt2x2_wgrad": ([P, I, P, I, P, P, I, I, I, I, I, I, P, Z, P], c_int),
     "pis_debug_convt2x2_wgrad_tile_splits": ([I, I, I, I, I], c_int),
+    "pis_debug_convt2x2_algo": ([I, I, I, I, I, I, I, I, I], c_int),
     "pis_maxpool2x2_fwd": ([P, I, P, I, I, I, I, P], c_int),
     "pis_maxpool2x2_bwd": ([P, I, P, P, I, P, I, I, I, I, I, P], c_int),
     "pis_head_fwd": ([P, I, P, P, P, P, L, I, P], c_int),

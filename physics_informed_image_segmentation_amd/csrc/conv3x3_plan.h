@@ -17,6 +17,31 @@ WgradPlan plan_wgrad(int Mp, int Np, int P, int group_m, int group_n, int target
 size_t wgrad_ws_bytes(const WgradPlan& pl);
 size_t colsum_ws(int64_t npix, int C);
 
+// the split-K kernel families of wgrad.hip (run_wgrad launches the one chosen, on the plan's tile)
+enum class WgradKernel {
+  F32,        // wgrad_f32_kernel: fp32 MFMA, every operand form
+  X6,         // wgrad_x6_kernel: bf16x6, operands staged by columns
+  H3_COLS,    // wgrad_h3_kernel: fp16x3, operands staged by columns
+  H3T,        // wgrad_h3t_kernel: fp16x3, operands staged by rows, 128 x 128 tiles
+  H3T_EXACT,  // ... its form for whole K-steps and 31-bit row offsets (h3t_exact)
+  H3T_TWIN,   // ... its timing twin (pis_tune key 2, wrong results)
+};
+constexpr int WT_BK = 32;  // pixels per K-step of the row-staged kernels
+// what the choice needs to know about a launch's operands A (rows lda) and B (rows ldb)
+struct WgradOperands {
+  bool plain;        // B is read as plain rows (not gathered from a 3x3 conv's taps)
+  bool a_up2;        // A is the transposed conv's dy at the up-sampled pixels
+  int W, P, Np;      // image width, pixels of the reduction, columns of B (plain: the input channels)
+  int lda, ldb;
+  int64_t bs_a, bs_b;  // batched launches: per-batch offsets
+  bool aligned16;      // both base pointers
+};
+// wgrad_h3t_kernel's EX form: whole K-steps in every split and 31-bit row offsets for the buffer
+// loads (the batch offsets go into the base pointers)
+bool h3t_exact(const WgradPlan& pl, const WgradOperands& o);
+// pis_tune keys 14 (arithmetic), 31 (row staging) and 2 (timing twins)
+WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o);
+
 struct HaloPlan {
   bool use;
   int splits, seg_per_split, nseg;

@@ -174,6 +174,30 @@ ConvDirPlan plan_dir(int B, int H, int W, int C, int N, bool is_dgrad, bool wino
 
 }  // namespace
 
+bool h3t_exact(const WgradPlan& pl, const WgradOperands& o) {
+  return o.P % WT_BK == 0 && pl.pps % WT_BK == 0 &&
+         ((int64_t)o.P + WT_BK) * std::max(o.a_up2 ? 0 : o.lda, o.ldb) * 4 < (int64_t(1) << 31);
+}
+
+WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o) {
+  // key 14 = 3 (auto): fp16x3 where the layer has >= 256 input channels. The bf16x6
+  // and fp16x3 kernels take plain B operands only, where Np IS the input-channel count (Winograd:
+  // Cin; convT: Cin); the 3x3 conv's gathered operand (Np = 9 Cin) runs the fp32 MFMA kernel. Their
+  // columns hold 8 pixels of an image row (a_up2: W % 8 == 0)
+  const int x6 = tune_get(PIS_TUNE_WGRAD_X6);
+  const bool cols = o.plain && pl.pps % 16 == 0 && (!o.a_up2 || o.W % 8 == 0);
+  if (cols && (x6 == 2 || (x6 == 3 && o.Np >= 256))) {
+    // key 31: the row-staged kernel for plain 128 x 128 tiles (float4 rows: 16-B aligned)
+    if (tune_get(PIS_TUNE_WGRAD_T) != 0 && pl.bm == 128 && pl.bn == 128 && !o.a_up2 && pl.pps % WT_BK == 0 &&
+        o.lda % 4 == 0 && o.ldb % 4 == 0 && o.bs_a % 4 == 0 && o.bs_b % 4 == 0 && o.aligned16)
+      return tune_get(PIS_TUNE_DEBUG_NOLOAD) ? WgradKernel::H3T_TWIN
+             : h3t_exact(pl, o)              ? WgradKernel::H3T_EXACT
+                                             : WgradKernel::H3T;
+    return WgradKernel::H3_COLS;
+  }
+  return (cols && x6 != 0) ? WgradKernel::X6 : WgradKernel::F32;
+}
+
 Conv3x3Plan plan_conv3x3(int B, int H, int W, int Cin, int Cout) {
   Conv3x3Plan p{};
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;

@@ -12,10 +12,10 @@
 //            Bt = w_cijo rows (pis_convt2x2_prep); the epilogue applies the ReLU mask of the
 //            convT input and optionally accumulates.
 // Block tile 128 x 128, 4 waves of 64 x 64 (2 x 2 32x32 MFMA tiles), K-step 16 through a
-// register-staged LDS double buffer; XCD-aware tile order. pis_tune key 13: 3 (default) fp16x3 on
-// fp16 MFMA (fp32-class, -3..-18 % per layer vs bf16x6, profiles/r2_q68_*), 1 bf16x6 on bf16 MFMA
-// (fp32-accurate), 2 native fp32 MFMA, 0 off (implicit-GEMM fallback).
-#include "igemm.h"
+// register-staged LDS double buffer; XCD-aware tile order. Three arithmetic arms: fp16x3 on fp16
+// MFMA (fp32-class, -3..-18 % per layer vs bf16x6, profiles/r2_q68_*), bf16x6 on bf16 MFMA
+// (fp32-accurate), native fp32 MFMA; which one a call runs: convt_plan.h.
+#include "convt_plan.h"
 
 namespace pis {
 
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void convt_gemm_kernel(ConvtGemmArgs g) {
 // epilogue goes through LDS per wave (32 rows x 64 columns at a time) so every lane finishes 4
 // consecutive channels of a pixel with 16-B accesses (forward: the 2 x 2 scatter, whole
 // 256-B pixel runs, + bias; input gradient: ReLU mask, accumulate). Needs M, N % 128, w % 32,
-// 16-B aligned operands and channel strides % 4 (launch_convt_gemm checks, else key 13 = 3).
+// 16-B aligned operands and channel strides % 4 (resolve_convt checks, else CONVT_GEMM_H3).
 template <int MODE>
 __global__ __launch_bounds__(256, 3) void convt_h3_kernel(ConvtGemmArgs g) {
   constexpr int BM = 128, BN = 128, BK = 32, KP = 32, AL = BM * 8 / 256, BL = BN * 8 / 256;
@@ -510,38 +510,26 @@ __global__ __launch_bounds__(256, 3) void convt_h3_kernel(ConvtGemmArgs g) {
   }
 }
 
-// 0 = handled, 1 = shape not covered (caller falls back to the implicit GEMM)
-int launch_convt_gemm(int mode, const float* a, int lda, const float* bt, int B, int h, int w, int cin, int cout,
-                      const float* bias, const float* mask, int ldm, float* dst, int ldd, int flags,
+// launches the resolved algorithm (convt_plan.h): one of CONVT_H3_K32 and the three CONVT_GEMM_* arms
+int launch_convt_gemm(ConvtAlgo algo, int mode, const float* a, int lda, const float* bt, int B, int h, int w, int cin,
+                      int cout, const float* bias, const float* mask, int ldm, float* dst, int ldd, int flags,
                       hipStream_t s) {
-  if (tune_get(PIS_TUNE_CONVT_GEMM) == 0 || cin % 16 || cout % 16 || lda % 4) return 1;
   ConvtGemmArgs g{};
   g.a = a; g.lda = lda; g.bt = bt; g.B = B; g.h = h; g.w = w; g.cin = cin; g.cout = cout;
   g.M = B * h * w;
   g.N = mode == 0 ? 4 * cout : cin;
   g.K = mode == 0 ? cin : 4 * cout;
   g.bias = bias; g.mask = mask; g.ldm = ldm; g.dst = dst; g.ldd = ldd; g.flags = flags;
-  const int grid = (int)(cdiv(g.M, 128) * cdiv(g.N, 128));
-  int v = tune_get(PIS_TUNE_CONVT_GEMM);
-  if (v == 4) {
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool ok = g.M % 128 == 0 && g.N % 128 == 0 && w % 32 == 0 && cout % 32 == 0 && cin % 32 == 0 &&
-                    lda % 4 == 0 && ldd % 4 == 0 && a16(a) && a16(bt) && a16(dst) &&
-                    (mode == 0 ? (!bias || a16(bias)) : (!(flags & PIS_MASK) || (a16(mask) && ldm % 4 == 0)));
-    if (ok) {
-      if (mode == 0) hipLaunchKernelGGL(convt_h3_kernel<0>, dim3(grid), dim3(256), 0, s, g);
-      else hipLaunchKernelGGL(convt_h3_kernel<1>, dim3(grid), dim3(256), 0, s, g);
-      return launch_status(mode == 0 ? "convt_h3_fwd" : "convt_h3_dgrad");
-    }
-    v = 3;
+  void (*fn)(ConvtGemmArgs) = nullptr;
+  switch (algo) {
+    case CONVT_H3_K32: fn = mode == 0 ? convt_h3_kernel<0> : convt_h3_kernel<1>; break;
+    case CONVT_GEMM_H3: fn = mode == 0 ? convt_gemm_kernel<0, 2> : convt_gemm_kernel<1, 2>; break;
+    case CONVT_GEMM_X6: fn = mode == 0 ? convt_gemm_kernel<0, 1> : convt_gemm_kernel<1, 1>; break;
+    case CONVT_GEMM_F32: fn = mode == 0 ? convt_gemm_kernel<0, 0> : convt_gemm_kernel<1, 0>; break;
+    default: return set_error("launch_convt_gemm: not a GEMM arm (%d)", (int)algo), PIS_ERR_ARG;
   }
-  const int ar = v == 1 ? 1 : v == 3 ? 2 : 0;  // 2 = fp32 MFMA
-  if (mode == 0 && ar == 2) hipLaunchKernelGGL((convt_gemm_kernel<0, 2>), dim3(grid), dim3(256), 0, s, g);
-  else if (mode == 0 && ar == 1) hipLaunchKernelGGL((convt_gemm_kernel<0, 1>), dim3(grid), dim3(256), 0, s, g);
-  else if (mode == 0) hipLaunchKernelGGL((convt_gemm_kernel<0, 0>), dim3(grid), dim3(256), 0, s, g);
-  else if (ar == 2) hipLaunchKernelGGL((convt_gemm_kernel<1, 2>), dim3(grid), dim3(256), 0, s, g);
-  else if (ar == 1) hipLaunchKernelGGL((convt_gemm_kernel<1, 1>), dim3(grid), dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((convt_gemm_kernel<1, 0>), dim3(grid), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(fn, dim3((unsigned)(cdiv(g.M, 128) * cdiv(g.N, 128))), dim3(256), 0, s, g);
+  if (algo == CONVT_H3_K32) return launch_status(mode == 0 ? "convt_h3_fwd" : "convt_h3_dgrad");
   return launch_status(mode == 0 ? "convt_gemm_fwd" : "convt_gemm_dgrad");
 }
 

@@ -125,9 +125,4 @@ size_t direct_w_ws_bytes(int B, int H, int W, int Cin, int Cout);
 int launch_direct_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw, float* db, int B, int H, int W,
                         int Cin, int Cout, int acc, void* ws, size_t ws_bytes, hipStream_t s);
 
-// transposed-conv GEMMs (convt.hip): 0 = launched, 1 = shape not covered, < 0 = error
-int launch_convt_gemm(int mode, const float* a, int lda, const float* bt, int B, int h, int w, int cin, int cout,
-                      const float* bias, const float* mask, int ldm, float* dst, int ldd, int flags,
-                      hipStream_t s);
-
 }  // namespace pis

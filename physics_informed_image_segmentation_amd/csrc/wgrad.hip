@@ -17,7 +17,7 @@
 //           Cin == 1:  n' = tap (9 of 64 columns used)
 // convT2x2: m' = (i, j, o),       A(p, ijo)   = dy[(2h+i, 2w+j)][o]
 //           n' = c,               B(p, c)     = x[p][c]
-#include "conv3x3_plan.h"
+#include "convt_plan.h"
 
 namespace pis {
 
@@ -1006,11 +1006,24 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3_kernel(WgradArgs g) {
 // K-step's MFMA stream. Wave (wm, wn): rows 64 wm .., columns 64 wn .. of the 128 x 128 tile.
 // LDS rows are 256 B; the 16-B chunk index is XORed with 4 (row & 3), so a transposed read's
 // 32-lane half (4 rows x 4 chunks) meets 64 distinct banks and a row store (32 lanes) too.
-constexpr int WT_BK = 32;                        // pixels per K-step
 constexpr int WT_PLANE = WT_BK * 128;            // fp16 per plane
 constexpr int WT_BUF = 4 * WT_PLANE;             // A hi, A lo, B hi, B lo
 
 __device__ __forceinline__ int wtsw(int row, int chunk) { return row * 128 + 8 * (chunk ^ ((row & 3) << 2)); }
+
+// ---- pieces shared by the two row-staged kernels (wgrad_h3t_kernel, wgrad_up2_tile_kernel) ----
+// (their transposed fragment read, accumulator re-expression and slab epilogue stay written out in
+// both: as shared functions they changed the kernels' code, profiles/convt_plan_codegen.txt)
+__device__ __forceinline__ float umax4(const float (&r)[4]) {  // r >= 0: bit-pattern max
+  return __uint_as_float(max(max(__float_as_uint(r[0]), __float_as_uint(r[1])),
+                             max(__float_as_uint(r[2]), __float_as_uint(r[3]))));
+}
+// fp16x3: lo * hi, hi * lo, hi * hi (smallest partial products first)
+__device__ __forceinline__ f32x16 h3_mfma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+}
 
 // UP2 (the transposed-conv weight gradient, pis_tune key 13 = 4): A(p, (i, j, o)) = dy at the
 // up-sampled pixel (2y + i, 2x + j) of low-resolution pixel p = (b, y, x); with W % 32 == 0 and
@@ -1118,10 +1131,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   };
   float sa_last = 0.f, sb_last = 0.f, sa_min = __builtin_inff(), sb_min = __builtin_inff();
   auto split_store = [&](const f32x4 (&xa)[4], const f32x4 (&xb)[4], int par, float& sa, float& sb) __attribute__((always_inline)) {
-    auto umax4 = [](const float (&r)[4]) __attribute__((always_inline)) {  // r >= 0: bit-pattern max
-      return __uint_as_float(max(max(__float_as_uint(r[0]), __float_as_uint(r[1])),
-                                 max(__float_as_uint(r[2]), __float_as_uint(r[3]))));
-    };
     const float ma = umax4(red[par][0]);
     const float mb = umax4(red[par][1]);
     sa = sa_last = h3_keep(sa_last, ma, sa_min);
@@ -1222,11 +1231,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][a], bf[0][b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][a], bf[1][b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][a], bf[0][b], acc[a][b], 0, 0, 0);
-        }
+        for (int b = 0; b < 2; ++b) acc[a][b] = h3_mfma3(af[0][a], af[1][a], bf[0][b], bf[1][b], acc[a][b]);
     }
   };
   using I0 = std::integral_constant<int, 0>;
@@ -1303,7 +1308,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
 // block multiplies meanwhile.
 // Needs W % 32 == 0 and pix_per_split % 32 == 0 (every split is whole K-steps of one image row),
 // Mp % 256 == 0, Np % 128 == 0, Ca % 4 == 0, lda / ldb % 4 == 0 and 16-B aligned operands.
-constexpr int WU_BM = 256, WU_BN = 128;
 constexpr int WU_LDS = 6 * WT_PLANE;  // fp16 elements
 
 __global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
@@ -1363,10 +1367,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
   };
   float sa = 0.f, sb = 0.f, sa_min = __builtin_inff(), sb_min = __builtin_inff();  // the staged K-step's scales
   auto split_store = [&](int par) __attribute__((always_inline)) {
-    auto umax4 = [](const float (&r)[4]) __attribute__((always_inline)) {  // r >= 0: bit-pattern max
-      return __uint_as_float(max(max(__float_as_uint(r[0]), __float_as_uint(r[1])),
-                                 max(__float_as_uint(r[2]), __float_as_uint(r[3]))));
-    };
     sa = h3_keep(sa, umax4(red[par][0]), sa_min);
     sb = h3_keep(sb, umax4(red[par][1]), sb_min);
 #pragma unroll
@@ -1442,11 +1442,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
       for (int a = 0; a < 4; ++a) {
         const f16x8 ah = frag(a_hi, ks, 32 * a), al = frag(a_lo, ks, 32 * a);
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf[0][b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf[1][b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf[0][b], acc[a][b], 0, 0, 0);
-        }
+        for (int b = 0; b < 2; ++b) acc[a][b] = h3_mfma3(ah, al, bf[0][b], bf[1][b], acc[a][b]);
       }
     }
     const bool more = st + 1 < nst;
@@ -1485,64 +1481,41 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
   }
 }
 
-// wgrad_h3t_kernel's EX form: whole K-steps in every split (pix_per_split is a multiple of 32) and
-// 31-bit row offsets for the buffer loads (the batch offsets go into the base pointers)
-static bool h3t_exact(const WgradArgs& a) {
-  return a.P % WT_BK == 0 && a.pix_per_split % WT_BK == 0 &&
-         ((int64_t)a.P + WT_BK) * std::max(a.a_up2 ? 0 : a.lda, a.ldb) * 4 < (int64_t(1) << 31);
+static WgradOperands wgrad_operands(const WgradArgs& a) {
+  return {a.b_mode == B_PLAIN, a.a_up2 != 0, a.W, a.P, a.Np, a.lda, a.ldb, a.bs_a, a.bs_b,
+          (((uintptr_t)a.a | (uintptr_t)a.b) & 15) == 0};
 }
 
-static int run_wgrad(const WgradArgs& base, const WgradPlan& pl, hipStream_t s, int batches = 1) {
+// one split-K launch: the planned kernel on the plan's tile
+static int run_wgrad(const WgradArgs& base, const WgradPlan& pl, WgradKernel k, hipStream_t s, int batches = 1) {
   WgradArgs a = base;
   a.pix_per_split = pl.pps;
   a.pair = tune_get(PIS_TUNE_WGRAD_PAIR);
   a.dbg = tune_get(PIS_TUNE_DEBUG_NOLOAD);
   const int tiles = (a.Mp / pl.bm) * (a.Np / pl.bn);
   const dim3 grid(tiles * pl.splits, batches);
-  // key 14 = 3 (auto): fp16x3 where the contraction's output has >= 256 columns (Cin): measured
-  // per layer (profiles/r2_q53_wgrad_fp16x3.txt) it wins on exactly those (-1..-10 %) and loses on
-  // the HBM-bound 64 / 128-channel layers (+1..+9 %). The split GEMMs take plain B operands only,
-  // where Np IS the input-channel count (Winograd: Cin; convT: Cin); the direct path's B_CONV3
-  // operand (Np = 9 Cin) never reaches them, it runs the fp32 MFMA kernel below
-  const int x6 = tune_get(PIS_TUNE_WGRAD_X6);
-  const bool plain = a.b_mode == B_PLAIN;
-  const int cin = plain ? a.Np : a.Cb;
-  if ((x6 == 2 || (x6 == 3 && cin >= 256)) && plain && pl.pps % 16 == 0 &&
-      (!a.a_up2 || a.W % 8 == 0)) {
-    // key 31: the row-staged kernel for plain 128 x 128 tiles (float4 rows: 16-B aligned)
-    if (tune_get(PIS_TUNE_WGRAD_T) != 0 && pl.bm == 128 && pl.bn == 128 && !a.a_up2 &&
-        pl.pps % WT_BK == 0 && a.lda % 4 == 0 && a.ldb % 4 == 0 && a.bs_a % 4 == 0 && a.bs_b % 4 == 0 &&
-        ((uintptr_t)a.a & 15) == 0 && ((uintptr_t)a.b & 15) == 0) {
-      if (a.dbg)
-        hipLaunchKernelGGL((wgrad_h3t_kernel<false, 2, true>), grid, dim3(256), 0, s, a);
-      else if (h3t_exact(a))
-        hipLaunchKernelGGL((wgrad_h3t_kernel<false, 2, false, true>), grid, dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((wgrad_h3t_kernel<false, 2>), grid, dim3(256), 0, s, a);
-      return launch_status("wgrad_h3t");
-    }
-    if (pl.bm == 128 && pl.bn == 128) hipLaunchKernelGGL((wgrad_h3_kernel<128, 128>), grid, dim3(256), 0, s, a);
-    else if (pl.bm == 128) hipLaunchKernelGGL((wgrad_h3_kernel<128, 64>), grid, dim3(256), 0, s, a);
-    else if (pl.bn == 128) hipLaunchKernelGGL((wgrad_h3_kernel<64, 128>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wgrad_h3_kernel<64, 64>), grid, dim3(256), 0, s, a);
-    return launch_status("wgrad_h3");
+  using Kernel = void (*)(WgradArgs);  // per family: tiles 64 x 64, 64 x 128, 128 x 64, 128 x 128
+  static const Kernel f32[4] = {wgrad_f32_kernel<64, 64, 32>, wgrad_f32_kernel<64, 128, 32>, wgrad_f32_kernel<128, 64, 32>,
+                                wgrad_f32_kernel<128, 128, 16>};
+  static const Kernel x6[4] = {wgrad_x6_kernel<64, 64>, wgrad_x6_kernel<64, 128>, wgrad_x6_kernel<128, 64>,
+                               wgrad_x6_kernel<128, 128>};
+  static const Kernel h3[4] = {wgrad_h3_kernel<64, 64>, wgrad_h3_kernel<64, 128>, wgrad_h3_kernel<128, 64>,
+                               wgrad_h3_kernel<128, 128>};
+  const int t = (pl.bm == 128 ? 2 : 0) + (pl.bn == 128 ? 1 : 0);
+  const bool up2 = a.a_up2 != 0;  // the row-staged kernels: 128 x 128 tiles only
+  Kernel fn = f32[t];
+  const char* name = "wgrad_f32";
+  switch (k) {
+    case WgradKernel::F32: break;
+    case WgradKernel::X6: fn = x6[t]; name = "wgrad_x6"; break;
+    case WgradKernel::H3_COLS: fn = h3[t]; name = "wgrad_h3"; break;
+    case WgradKernel::H3T: fn = up2 ? wgrad_h3t_kernel<true, 2> : wgrad_h3t_kernel<false, 2>; break;
+    case WgradKernel::H3T_EXACT: fn = up2 ? wgrad_h3t_kernel<true, 2, false, true> : wgrad_h3t_kernel<false, 2, false, true>; break;
+    case WgradKernel::H3T_TWIN: fn = wgrad_h3t_kernel<false, 2, true>; break;
   }
-  if (x6 != 0 && a.b_mode == B_PLAIN && pl.pps % 16 == 0 && (!a.a_up2 || a.W % 8 == 0)) {
-    if (pl.bm == 128 && pl.bn == 128) hipLaunchKernelGGL((wgrad_x6_kernel<128, 128>), grid, dim3(256), 0, s, a);
-    else if (pl.bm == 128) hipLaunchKernelGGL((wgrad_x6_kernel<128, 64>), grid, dim3(256), 0, s, a);
-    else if (pl.bn == 128) hipLaunchKernelGGL((wgrad_x6_kernel<64, 128>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wgrad_x6_kernel<64, 64>), grid, dim3(256), 0, s, a);
-    return launch_status("wgrad_x6");
-  }
-  if (pl.bm == 128 && pl.bn == 128)
-    hipLaunchKernelGGL((wgrad_f32_kernel<128, 128, 16>), grid, dim3(256), 0, s, a);
-  else if (pl.bm == 128)
-    hipLaunchKernelGGL((wgrad_f32_kernel<128, 64, 32>), grid, dim3(256), 0, s, a);
-  else if (pl.bn == 128)
-    hipLaunchKernelGGL((wgrad_f32_kernel<64, 128, 32>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((wgrad_f32_kernel<64, 64, 32>), grid, dim3(256), 0, s, a);
-  return launch_status("wgrad_f32");
+  if (k >= WgradKernel::H3T) name = up2 ? "wgrad_h3t<up2>" : "wgrad_h3t";
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, a);
+  return launch_status(name);
 }
 
 }  // namespace pis
@@ -1694,7 +1667,7 @@ static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* 
   a.split_stride = (int64_t)p.nxi * Cout * Cin;
   const double flop = 2.0 * p.nxi * (double)p.T * Cout * Cin;
   launch_hook("wino_wgrad_gemm", 0, s, flop);
-  rc = run_wgrad(a, p.gemm, s, p.nxi);
+  rc = run_wgrad(a, p.gemm, choose_wgrad_kernel(p.gemm, wgrad_operands(a)), s, p.nxi);
   launch_hook("wino_wgrad_gemm", 1, s, flop);
   // up to 16 split slabs: the output transform sums them itself (no reduced copy of the 36 planes:
   // the separate slab reduction of a 14-slab 128 x 256 layer read 66 MB at 0.8 TB/s); many slabs
@@ -1837,7 +1810,7 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
   a.B = B; a.H = H; a.W = W; a.P = B * H * W; a.Mp = Cout; a.Np = Cin == 1 ? 64 : 9 * Cin;
   a.part = (float*)ws;
   a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
-  int rc = run_wgrad(a, pl, s);
+  int rc = run_wgrad(a, pl, choose_wgrad_kernel(pl, wgrad_operands(a)), s);
   if (rc) return rc;
   if (Cin == 1) {
     float* full = (float*)((char*)ws + wgrad_ws_bytes(pl));
@@ -1854,57 +1827,6 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
   return reduce_slabs(a.part_bias, pl.splits, Cout, db, acc, s);
 }
 
-// key 13 = 4: the transposed-conv weight gradient on the row-staged fp16x3 kernel (wgrad_h3t<UP2>)
-// where it has >= 256 input channels (up2 -11 %, up3 -12 %, up4 -25 %; up1, 128 -> 64 at 256^2,
-// +17 %: it keeps the bf16x6 column-staged kernel; profiles/r3_q17_convt.txt)
-static bool convt_wgrad_t_ok(int B, int H, int W, int Cin, int Cout, int ldx, int lddy, const void* x,
-                             const void* dy) {
-  return tune_get(PIS_TUNE_CONVT_GEMM) == 4 && W % 32 == 0 && (4 * Cout) % 128 == 0 && Cin >= 256 && Cin % 128 == 0 &&
-         ldx % 4 == 0 && lddy % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
-         plan_wgrad(4 * Cout, Cin, B * H * W, 4 * Cout, Cin).pps % WT_BK == 0;
-}
-
-// key 56: the 256 x 128 tile kernel (wgrad_up2_tile_kernel). One resident generation, tiles x splits
-// about 512 blocks (two per CU); pps a multiple of the K-step, chains of 512 .. 8192 pixels
-static bool convt_wgrad_tile_shape(int W, int Cin, int Cout) {
-  return W % WT_BK == 0 && Cin % WU_BN == 0 && (4 * Cout) % WU_BM == 0;
-}
-
-static WgradPlan plan_convt_tile(int Mp, int Np, int P) {
-  WgradPlan p{};
-  p.bm = WU_BM;
-  p.bn = WU_BN;
-  const int tiles = (Mp / WU_BM) * (Np / WU_BN);
-  const int64_t want_splits = std::max<int64_t>(1, cdiv(512, tiles));
-  int64_t pps = std::min<int64_t>(std::max<int64_t>(512, cdiv(P, want_splits)), 8192);
-  pps = cdiv(pps, WT_BK) * WT_BK;
-  p.pps = (int)pps;
-  p.splits = (int)cdiv(P, pps);
-  p.part_bytes = (size_t)p.splits * Mp * Np * sizeof(float);
-  p.bias_bytes = (size_t)p.splits * Mp * sizeof(float);
-  return p;
-}
-
-static bool convt_wgrad_tile_ok(int W, int Cin, int Cout, int ldx, int lddy, const void* x, const void* dy) {
-  return tune_get(PIS_TUNE_CONVT_WGRAD_TILE) != 0 && tune_get(PIS_TUNE_CONVT_GEMM) == 4 &&
-         convt_wgrad_tile_shape(W, Cin, Cout) && ldx % 4 == 0 && lddy % 4 == 0 && ((uintptr_t)x & 15) == 0 &&
-         ((uintptr_t)dy & 15) == 0;
-}
-
-extern "C" size_t pis_convt2x2_wgrad_ws(int B, int H, int W, int Cin, int Cout) {
-  // the maximum over every plan (keys 13 and 56 may change after the workspace is sized)
-  size_t n = std::max(wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, Cout, Cin)),
-                      wgrad_ws_bytes(plan_wgrad(4 * Cout, Cin, B * H * W, 4 * Cout, Cin)));
-  if (convt_wgrad_tile_shape(W, Cin, Cout)) n = std::max(n, wgrad_ws_bytes(plan_convt_tile(4 * Cout, Cin, B * H * W)));
-  return n;
-}
-
-// tooling and tests: the splits of the 256 x 128 tile plan (0 where the shape is outside its contract)
-extern "C" int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !convt_wgrad_tile_shape(W, Cin, Cout)) return 0;
-  return plan_convt_tile(4 * Cout, Cin, B * H * W).splits;
-}
-
 extern "C" int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw_ijoc,
                                   float* db, int B, int H, int W, int Cin, int Cout, int flags,
                                   void* ws, size_t ws_bytes, pis_stream_t stream) {
@@ -1912,54 +1834,29 @@ extern "C" int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int 
                 "pis_convt2x2_wgrad: bad arguments");
   PIS_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0, "pis_convt2x2_wgrad: Cin/Cout must be multiples of 64");
   PIS_CHECK_ARG(ldx % 4 == 0 && lddy % 4 == 0, "pis_convt2x2_wgrad: ld must be multiples of 4");
-  PIS_CHECK_ARG(ws && ws_bytes >= pis_convt2x2_wgrad_ws(B, H, W, Cin, Cout),
-                "pis_convt2x2_wgrad: workspace too small");
+  const ConvtPlan p = plan_convt2x2(B, H, W, Cin, Cout);
+  PIS_CHECK_ARG(ws && ws_bytes >= p.wgrad_ws, "pis_convt2x2_wgrad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int acc = flags & PIS_ACCUMULATE;
-  const int P = B * H * W;
-  if (convt_wgrad_tile_ok(W, Cin, Cout, ldx, lddy, x, dy)) {
-    const WgradPlan pl = plan_convt_tile(4 * Cout, Cin, P);
-    WgradArgs a{};
-    a.a = dy; a.lda = lddy; a.a_up2 = 1; a.Ca = Cout;
-    a.b = x; a.ldb = ldx; a.b_mode = B_PLAIN; a.Cb = Cin;
-    a.B = B; a.H = H; a.W = W; a.P = P; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
-    a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
-    a.pix_per_split = pl.pps;
-    const int tiles = (a.Mp / WU_BM) * (a.Np / WU_BN);
-    hipLaunchKernelGGL(wgrad_up2_tile_kernel, dim3(tiles * pl.splits), dim3(256), 0, s, a);
-    int rc = launch_status("wgrad_up2_tile");
-    if (!rc) rc = reduce_slabs2(a.part, pl.splits, (int64_t)a.Mp * a.Np, dw_ijoc, a.part_bias, pl.splits * 4, Cout, db,
-                                acc, s);
-    return rc;
-  }
-  if (convt_wgrad_t_ok(B, H, W, Cin, Cout, ldx, lddy, x, dy)) {
-    const WgradPlan pl = plan_wgrad(4 * Cout, Cin, P, 4 * Cout, Cin);  // 128 x 128 tiles (taps may share one)
-    WgradArgs a{};
-    a.a = dy; a.lda = lddy; a.a_up2 = 1; a.Ca = Cout;
-    a.b = x; a.ldb = ldx; a.b_mode = B_PLAIN; a.Cb = Cin;
-    a.B = B; a.H = H; a.W = W; a.P = P; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
-    a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
-    a.pix_per_split = pl.pps;
-    const int tiles = (a.Mp / 128) * (a.Np / 128);
-    if (h3t_exact(a))
-      hipLaunchKernelGGL((wgrad_h3t_kernel<true, 2, false, true>), dim3(tiles * pl.splits), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((wgrad_h3t_kernel<true, 2>), dim3(tiles * pl.splits), dim3(256), 0, s, a);
-    int rc = launch_status("wgrad_h3t<up2>");
-    // weights + bias (slabs [split][i][j][o]: 4 splits slabs of Cout) in one launch
-    if (!rc) rc = reduce_slabs2(a.part, pl.splits, (int64_t)a.Mp * a.Np, dw_ijoc, a.part_bias, pl.splits * 4, Cout, db,
-                                acc, s);
-    return rc;
-  }
-  const WgradPlan pl = plan_wgrad(4 * Cout, Cin, P, Cout, Cin);
+  const ConvtWgradChoice c = resolve_convt_wgrad(p, {ldx, lddy, (((uintptr_t)x | (uintptr_t)dy) & 15) == 0});
+  const WgradPlan& pl = c.pl;
   WgradArgs a{};
   a.a = dy; a.lda = lddy; a.a_up2 = 1; a.Ca = Cout;
   a.b = x; a.ldb = ldx; a.b_mode = B_PLAIN; a.Cb = Cin;
-  a.B = B; a.H = H; a.W = W; a.P = P; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
+  a.B = B; a.H = H; a.W = W; a.P = B * H * W; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
   a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
-  int rc = run_wgrad(a, pl, s);
+  int rc = PIS_ERR_ARG;
+  switch (c.algo) {
+    case CONVT_WGRAD_TILE:
+      a.pix_per_split = pl.pps;
+      hipLaunchKernelGGL(wgrad_up2_tile_kernel, dim3((a.Mp / WU_BM) * (a.Np / WU_BN) * pl.splits), dim3(256), 0, s, a);
+      rc = launch_status("wgrad_up2_tile");
+      break;
+    case CONVT_WGRAD_ROWS_UP2:
+    case CONVT_WGRAD_SPLITK: rc = run_wgrad(a, pl, c.kernel, s); break;
+    case CONVT_WGRAD_NONE: break;
+  }
   // weights + bias (slabs [split][i][j][o]: 4 splits slabs of Cout) in one launch
   if (!rc) rc = reduce_slabs2(a.part, pl.splits, (int64_t)a.Mp * a.Np, dw_ijoc, a.part_bias, pl.splits * 4, Cout, db,
-                              acc, s);
+                              flags & PIS_ACCUMULATE, s);
   return rc;
 }
