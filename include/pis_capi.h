@@ -275,7 +275,17 @@ int pis_version(void);
                                  The key may change between any two calls: pis_convt2x2_wgrad_ws is the maximum
                                  over every plan. The contract and the only code that reads the key: the planner,
                                  csrc/convt_plan.h ("Transposed-conv arms") */
-#define PIS_TUNE_NKEYS 57
+#define PIS_TUNE_UNROLL_TB 57 /* pis_pde_unroll_fwd / pis_pde_unroll_bwd (csrc/evolve.hip) called with tb = 0: Tb, the
+                                 explicit steps one checkpoint spans and one reverse launch sweeps back inside LDS:
+                                 1, 2 or 4, anything else is PIS_ERR_ARG. Every value gives the same bits. The rule
+                                 for the default, fixed before measuring: the lowest forward-plus-backward time of
+                                 16 steps at 8 x 512^2, mu = 0, clamp on. Default 2: about 279 us there against
+                                 303 (Tb = 4) and 400 (Tb = 1); at 64 x 128^2 Tb = 4 is 3 % ahead of 2
+                                 (tools/bench_unroll.py, profiles/pde_unroll.txt). The checkpoint stack is
+                                 ceil(steps / Tb) - 1 maps. A forward and its backward must use the same Tb: a
+                                 caller that cannot rule out a change of the key in between reads it once and
+                                 passes tb explicitly (pde.py does) */
+#define PIS_TUNE_NKEYS 58
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -880,6 +890,45 @@ int pis_pde_evolve(const float* u, const float* u0, float* out, uint8_t* mask, i
 size_t pis_pde_energies_ws(int B, int H, int W);
 int pis_pde_energies(const float* u, int B, int H, int W, float D, float a, float eps, double* out_f64,
                      int64_t* out_i64, void* ws, size_t ws_bytes, pis_stream_t stream);
+
+/* ---- the evolution above as a differentiable layer: checkpointed forward and reverse sweep (no reference
+ * counterpart; pde.py:unroll_vjp_np is the definition of record and agrees bit for bit) ----
+ * tb is the temporal block Tb in {1, 2, 4}; 0 reads pis_tune key PIS_TUNE_UNROLL_TB. The same Tb must be
+ * given to the forward and to its backward.
+ *
+ * pis_pde_unroll_fwd: pis_pde_evolve's steps (same kernel, same bits in out) in ceil(steps / Tb) launches;
+ * launch i < the last writes the state after (i + 1) Tb steps into map i of ckpt (16-byte aligned,
+ * pis_pde_unroll_ws(B, H, W, steps, tb) bytes = ceil(steps / Tb) - 1 maps, each rounded up to 16 bytes), the
+ * last writes out. steps == 0 copies u.
+ *
+ * pis_pde_unroll_bwd: given g_out = dL/d out, writes g_u = dL/du and, when u0 was given, g_u0 = dL/du0 (g_u0
+ * may be NULL if it is not wanted; with u0 NULL it must be). Per step, last first, with c the step's input, n
+ * its update before the clamp and g' the gradient with respect to its output:
+ *   q  = (n < 0 or n > 1) and PIS_EVOLVE_CLAMP ? 0 : g'
+ *   nb = (wa_H[y] q[y-1][x] + wb_H[y] q[y+1][x]) + (wa_W[x] q[y][x-1] + wb_W[x] q[y][x+1])
+ *        wa[i] = 0, 2, 1, 1, ...: i = 0, 1, 2, ...      wb[i] = 0, 2, 1, 1, ...: i = n-1, n-2, n-3, ...
+ *        (the transpose of the reflect padding; a q outside the image is 0)
+ *   rp = ((1 - 2 c) (c - a)) + (c (1 - c));  s = k rp;  s = s - (4 D);  if mu != 0: s = s - mu
+ *   g  = (1 + dt s) q + (dt D) nb;           if mu != 0: gz = gz + (dt mu) q
+ * every operation float32 and rounded on its own, 4 D, dt D and dt mu formed once. g_u0 = gz; with u0 NULL
+ * g_u = g + gz (one add, also when mu == 0). steps == 0: g_u = g_out as bits, g_u0 = 0.
+ * One launch per temporal block, last block first: a workgroup reloads the block's starting state (u or a
+ * checkpoint) with a 2 Tb halo through reflect, recomputes the Tb states in LDS and sweeps the gradient back
+ * as a gather: no atomics, no halo exchange, bitwise reproducible and independent of Tb. The gradient passes
+ * through two maps in ws in turn; gz is carried in g_u0 (or a third map of ws), each tile touching its own
+ * pixels only. ws: 16-byte aligned, pis_pde_unroll_bwd_ws(B, H, W) bytes. No host synchronisation.
+ * PIS_ERR_ARG before any GPU work: as pis_pde_evolve, with steps in [0, PIS_UNROLL_MAX_STEPS] (the bound on
+ * the checkpoint stack; a choice), an illegal tb or key, g_u0 without u0, a missing or short ckpt or ws, and
+ * any written range (out, ckpt; g_u, g_u0, ws) overlapping another argument. The size queries answer 0. */
+#define PIS_UNROLL_MAX_STEPS 1024
+size_t pis_pde_unroll_ws(int B, int H, int W, int steps, int tb);
+size_t pis_pde_unroll_bwd_ws(int B, int H, int W);
+int pis_pde_unroll_fwd(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B, int H, int W,
+                       float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
+                       pis_stream_t stream);
+int pis_pde_unroll_bwd(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u, float* g_u0,
+                       int B, int H, int W, float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
+                       void* ws, size_t ws_bytes, pis_stream_t stream);
 
 /* ---- exact squared Euclidean distance transform of a batch of binary images, and the per-pixel
  * surface distances between two boundary maps (no reference counterpart;

@@ -1,9 +1,11 @@
 """CLI of the reference (main.py:5-102): same flags and defaults, training on
 the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
 --device-cache, --augment {flip,d4,affine}, --clip-grad-norm FLOAT,
---skip-nonfinite, --ema-decay FLOAT, --no-ema-warmup."""
+--skip-nonfinite, --ema-decay FLOAT, --no-ema-warmup, --pde-layer {rd,pf} with
+--pde-layer-steps N and --pde-layer-{dt,mu,diffusion,threshold-a,epsilon}."""
 import argparse
 
+from physics_informed_image_segmentation_amd.pde import add_refine_flags, refine_from_args
 from physics_informed_image_segmentation_amd.train import train
 
 
@@ -41,7 +43,9 @@ def parse_args(argv=None):
                         "fused AdamW step; validation, early stopping and evaluation use it (default: off)")
     p.add_argument("--no-ema-warmup", action="store_true",
                    help="use --ema-decay from the first step instead of min(decay, (1 + k) / (10 + k))")
+    add_refine_flags(p, prefix="pde-layer")
     a = p.parse_args(argv)
+    a.pde_layer_refine = refine_from_args(p, a, prefix="pde-layer")
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
         p.error("--clip-grad-norm must be positive")
     if a.ema_decay is not None and not 0.0 < a.ema_decay < 1.0:
@@ -62,7 +66,8 @@ def main(argv=None):
                  synthetic=tuple(a.synthetic) if a.synthetic else None,
                  device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment,
                  max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
-                 ema_decay=a.ema_decay, ema_warmup=not a.no_ema_warmup)
+                 ema_decay=a.ema_decay, ema_warmup=not a.no_ema_warmup,
+                 pde_layer=a.pde_layer_refine)
 
 
 if __name__ == "__main__":

@@ -24,8 +24,8 @@ from .evaluate import (ProbabilityTable, best_threshold_batch, boundary_counts, 
 from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
-from .pde import (PDERefine, PDERegularization, create_pde_regularization, energies, energies_np, evolve,  # noqa: E402
-                  evolve_np)
+from .pde import (PDELayer, PDERefine, PDERegularization, RefinedModel, create_pde_regularization, energies,  # noqa: E402
+                  energies_np, evolve, evolve_np, unroll, unroll_vjp_np)
 from .train import EarlyStopping, train, train_epoch, train_stage, validate  # noqa: E402
 from .unet import UNet, count_parameters  # noqa: E402
 from .evaluate_comparison import evaluate_and_compare, run_repeated_evaluations  # noqa: E402
@@ -46,5 +46,6 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "compute_ece_batch", "compute_brier_batch", "best_threshold_batch", "ProbabilityTable",
            "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np",
            "PDERefine", "evolve", "evolve_np", "energies", "energies_np",
+           "unroll", "unroll_vjp_np", "PDELayer", "RefinedModel",
            "distance_transform_sq", "distance_transform_sq_np", "surface_distances",
            "compute_hausdorff_percentile_batch", "compute_assd_batch", "compute_surface_dice_batch"]

@@ -25,6 +25,8 @@ PIS_TUNE_PROB_VARIANT = 52 # include/pis_capi.h: pis_probability_table kernel fo
 PIS_TUNE_EVOLVE_T = 54  # include/pis_capi.h: steps per launch of pis_pde_evolve (1, 2, 4 or 8)
 PIS_TUNE_EDT_PRUNE = 55  # include/pis_capi.h: what the distance transform's outward search skips (0, 1 or 3)
 PIS_TUNE_CONVT_WGRAD_TILE = 56  # include/pis_capi.h: transposed-conv weight gradient on 256 x 128 tiles (1) or the older kernels (0)
+PIS_TUNE_UNROLL_TB = 57  # include/pis_capi.h: steps per checkpoint and per reverse launch of pis_pde_unroll_* (1, 2 or 4)
+PIS_UNROLL_MAX_STEPS = 1024
 PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
@@ -125,6 +127,11 @@ _SIGNATURES = {
     "pis_pde_evolve_ws": ([I, I, I, I], c_size_t),
     "pis_pde_evolve": ([P, P, P, P, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, c_float, P, Z, P],
                        c_int),
+    "pis_pde_unroll_ws": ([I, I, I, I, I], c_size_t),
+    "pis_pde_unroll_bwd_ws": ([I, I, I], c_size_t),
+    "pis_pde_unroll_fwd": ([P, P, P, P, Z, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, I, P], c_int),
+    "pis_pde_unroll_bwd": ([P, P, P, P, P, P, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, I, P, Z, P],
+                           c_int),
     "pis_pde_energies_ws": ([I, I, I], c_size_t),
     "pis_pde_energies": ([P, I, I, I, c_float, c_float, c_float, P, P, P, Z, P], c_int),
     "pis_edt_ws": ([I, I, I], c_size_t),

@@ -255,14 +255,21 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
                          ablation_folder: Optional[Path] = None, num_workers: int = 2, boundary_metrics: bool = True,
                          verbose: bool = False, device_cache: bool = False, augment=None,
                          max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
-                         ema_decay: Optional[float] = None, ema_warmup: bool = True) -> Dict:
+                         ema_decay: Optional[float] = None, ema_warmup: bool = True, pde_layer=None) -> Dict:
     """Train one variant and evaluate it on both test sets (src/ablation.py:157-1237); same
     positional signature as the reference (``train_dir`` may be a ``DataSpec`` instead).
     ``device_cache=True`` keeps the four datasets resident on the GPU and assembles the batches there
     (``dataset.DeviceCachedLoader``; ``augment`` on the training loader only); a set that does not fit
     keeps its ``DataLoader``. ``max_grad_norm`` / ``skip_nonfinite`` go to every stage's ``AdamW``, and so do
     ``ema_decay`` / ``ema_warmup``: each stage then validates on its exponential moving average of the
-    weights and the test-set evaluations that follow a stage run on that average (``optim.AdamW``)."""
+    weights and the test-set evaluations that follow a stage run on that average (``optim.AdamW``).
+    ``pde_layer`` (a ``pde.PDERefine``, off by default): a variant's PDE stage (``config.use_pde``) trains and
+    validates ``pde.RefinedModel(model, pde_layer)``, as ``train(pde_layer=...)`` does; the evaluations after it
+    pass ``refine=pde_layer`` unless a Stage III without the layer followed, the saved weights stay the U-Net's,
+    and the result records the layer under ``"pde_layer"``."""
+    if pde_layer is not None:
+        from .pde import PDELayer
+        PDELayer(pde_layer)  # TypeError / ValueError before any work
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     data = _data_spec(train_dir, (train_json, val_dir, val_json, in_dist_test_dir, in_dist_test_json,
@@ -298,22 +305,24 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
 
     opts = []  # the stages' optimizers: the last one holds the current average
 
-    def evaluate():
+    def evaluate(refine=None):
+        kw = {} if refine is None else {"refine": refine}
         with opts[-1].averaged_weights() if ema_decay is not None and opts else contextlib.nullcontext():
-            return {"in_dist": evaluate_model(model, in_loader, device, 0.5, boundary_metrics),
-                    "out_dist": evaluate_model(model, out_loader, device, 0.5, boundary_metrics)}
+            return {"in_dist": evaluate_model(model, in_loader, device, 0.5, boundary_metrics, **kw),
+                    "out_dist": evaluate_model(model, out_loader, device, 0.5, boundary_metrics, **kw)}
 
-    def stage(criterion, epochs, name, csv_name):
+    def stage(criterion, epochs, name, csv_name, net=None):
         opt = AdamW(model.parameters(), lr=learning_rate, weight_decay=1e-5, max_grad_norm=max_grad_norm,
                     skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
         opts.append(opt)
         stop = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
-        return train_stage(model, train_loader, val_loader, criterion.to(device), opt, device, num_epochs=epochs,
-                           stage_name=name, early_stopping=stop, verbose=verbose,
+        return train_stage(model if net is None else net, train_loader, val_loader, criterion.to(device), opt, device,
+                           num_epochs=epochs, stage_name=name, early_stopping=stop, verbose=verbose,
                            csv_path=folder / f"{_slug(config.name)}_{csv_name}_metrics.csv")
 
     result: Dict = {"config": config.to_dict()}
     three = config.use_three_stage
+    final_refine = None  # the layer the last trained stage ran under
     if (config.use_two_stage and config.use_pde) or three:
         ep1 = config.stage1_epochs if config.stage1_epochs is not None else (50 if three else stage1_epochs)
         best1, bep1, _ = stage(DiceBCELoss(0.5, 0.5), ep1, "Stage I", "stage1")
@@ -329,8 +338,14 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
             ep2 = config.stage2_epochs if config.stage2_epochs is not None else stage2_epochs
         else:
             ep2 = config.stage1_epochs if config.stage1_epochs is not None else stage1_epochs
+        net = None
+        if pde_layer is not None and config.use_pde:
+            from .pde import RefinedModel
+            net = RefinedModel(model, pde_layer)
+            result["pde_layer"] = pde_layer.kwargs()
+            final_refine = None if three else pde_layer
         best2, bep2, _ = stage(create_ablation_loss(config), ep2,
-                               "Stage II (PDE)" if config.use_two_stage else "Training", "stage2")
+                               "Stage II (PDE)" if config.use_two_stage else "Training", "stage2", net=net)
         result["stage2_best_epoch"] = bep2
     if three:
         ep3 = config.stage3_epochs if config.stage3_epochs is not None else (config.stage2_epochs or stage2_epochs)
@@ -338,7 +353,7 @@ def run_ablation_variant(config: AblationConfig, train_dir, train_json=None, val
     path = folder / f"{_slug(config.name)}_final.pth"
     torch.save(model.state_dict(), path)
     result["model_path"] = str(path)
-    final = evaluate()
+    final = evaluate(final_refine)
     result["in_dist_metrics"] = {k: v.tolist() for k, v in final["in_dist"].items()}
     result["out_dist_metrics"] = {k: v.tolist() for k, v in final["out_dist"].items()}
     result["in_dist_summary"] = _summary(final["in_dist"])

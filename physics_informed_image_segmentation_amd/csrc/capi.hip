@@ -17,7 +17,7 @@ void set_error(const char* fmt, ...) {
 // kernel-variant knobs (defaults = the measured best on MI355X)
 static std::atomic<int> g_tune[PIS_TUNE_NKEYS] = {0, 16, 0, 1, 0, 1, 512, 0, 1, 1024, 4, 1, 0, 4, 3, 1, 1, 2,
                                                    1, 1, 1, 0, 1, 0, 0, 0, 2, 1, 0, 1, 0, 1, 1, 0, 0, 512, 0, 0, 1, 2, 2, 0, 1, 1, 0, 0, 1,
-                                                   0, 1, 2, 1, 1, 0, 3, 8, 3, 1};
+                                                   0, 1, 2, 1, 1, 0, 3, 8, 3, 1, 2};
 
 int tune_get(int key) { return (key > 0 && key < PIS_TUNE_NKEYS) ? g_tune[key].load() : 0; }
 
@@ -98,6 +98,10 @@ extern "C" int pis_tune(int key, int value) {
   }
   if (key == PIS_TUNE_EVOLVE_T && value >= 0 && value != 1 && value != 2 && value != 4 && value != 8) {
     pis::set_error("pis_tune: the temporal block of pis_pde_evolve must be 1, 2, 4 or 8");
+    return PIS_ERR_ARG;
+  }
+  if (key == PIS_TUNE_UNROLL_TB && value >= 0 && value != 1 && value != 2 && value != 4) {
+    pis::set_error("pis_tune: the temporal block of pis_pde_unroll_fwd / _bwd must be 1, 2 or 4");
     return PIS_ERR_ARG;
   }
   if (key == PIS_TUNE_EDT_PRUNE && value >= 0 && value != 0 && value != 1 && value != 3) {

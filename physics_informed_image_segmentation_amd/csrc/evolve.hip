@@ -6,6 +6,9 @@
 //                      on the reflect-padded 5-point stencil, T steps per launch inside LDS
 //   pis_pde_energies   per image: mean squared reaction-diffusion residual, mean phase-field energy
 //                      density, count of interface pixels; float64 sums in a fixed order
+//   pis_pde_unroll_fwd pis_pde_evolve's steps, keeping the state after every Tb-th step
+//   pis_pde_unroll_bwd the vector-Jacobian product of those steps, one launch per Tb steps, last first
+//                      (pde.py:unroll_vjp_np is its definition of record)
 //
 // Temporal blocking: a block owns an EV_TH x EV_TW output tile. It loads the tile plus a T-wide halo
 // through the reflect index (any number of periods: an image may be narrower than the halo), then
@@ -22,6 +25,10 @@ namespace pis {
 
 constexpr int EV_TH = PIS_EVOLVE_TILE_H, EV_TW = PIS_EVOLVE_TILE_W;
 constexpr int EV_THREADS = 256;
+// the reverse sweep: its planes let one (Tb = 4) or two (Tb = 2) workgroups reside on a CU, so the waves
+// come from the workgroup: 16 steps at 8 x 512^2, Tb = 2, took 438.9 us with 256 threads, 318.9 with 512
+// and 278.7 with 1024 (forward included; profiles/pde_unroll.txt holds the shipped form)
+constexpr int UN_THREADS = 1024;
 
 // the header's reflect(i, n), n >= 2, any number of periods out (infer.hip:tile_reflect)
 __device__ __forceinline__ int ev_reflect(int i, int n) {
@@ -139,6 +146,151 @@ __global__ __launch_bounds__(EV_THREADS) void pde_evolve_kernel(EvolveArgs g) {
         }
       }
     }
+  }
+}
+
+// ---- unrolled evolution: the reverse sweep (pde.py:unroll_vjp_np is the definition) ---
+// A block owns an EV_TH x EV_TW tile of the gradient with respect to the state a temporal block of
+// h <= T steps started from. The plane carries a 2 T halo: the block's starting state comes through
+// the reflect index, the incoming gradient from the image itself (zero outside it). The h states are
+// recomputed as in pde_evolve_kernel, kept before the clamp (n_s in st[s], exact s rings inside the
+// plane): the clamp is applied when a state is read and the pass mask is read off the same value.
+// The reverse step j (from c_(j+1) back to c_j) is a gather: it reads q = mask . g at the pixel and
+// its four neighbours and c_j at the pixel, so after it g is exact 2 h - j rings inside the plane,
+// 2 h <= 2 T for j = 0: the tile. The two gradient planes hold 0 outside the image and are never
+// written there, which is the definition's "pixels outside the image contribute 0". A sweep covers
+// a linear range of rows [r, PH - r) as the forward's does; what it writes less than r rings inside
+// is never read by an exact element.
+struct UnrollBwdArgs {
+  const float* src;  // the state the block starts from: u or a checkpoint
+  const float* u0;   // MU only
+  const float* gin;  // gradient with respect to the block's last state
+  float* gout;       // gradient with respect to src; never gin
+  float* gz;         // MU: the running sum of (dt mu) q, read (unless first) and written on the tile only
+  int H, W, nbx, nby, h;
+  int first, fold;   // first: gz starts from 0; fold: gout = g + gz (u is its own u0, last launch)
+  float k, a, mu, dt, fourD, dtD, dtmu;
+  float D;
+};
+
+__device__ __forceinline__ float un_clamp(float n) {
+  n = n < 0.f ? 0.f : n;
+  return n > 1.f ? 1.f : n;
+}
+
+template <int T>
+constexpr size_t un_lds_bytes(bool mu) {
+  constexpr size_t PN = (size_t)(EV_TH + 4 * T) * (EV_TW + 4 * T);
+  return sizeof(float) * ((T + 3) * PN + (mu ? PN + (size_t)EV_TH * EV_TW : 0));
+}
+
+template <bool MU, bool CLAMP, int T>
+__global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArgs g) {
+  constexpr int R = 2 * T, PH = EV_TH + 2 * R, PW = EV_TW + 2 * R, PN = PH * PW;
+  extern __shared__ __attribute__((aligned(16))) float un_lds[];
+  float* const st = un_lds;             // [T + 1][PN]: c_0, then n_1 .. n_h before the clamp
+  float* const gp = st + (T + 1) * PN;  // [2][PN]
+  float* const z = gp + 2 * PN;         // MU: [PN] u0
+  float* const gzt = z + PN;            // MU: [EV_TH * EV_TW]
+  const int tid = threadIdx.x;
+  const int bx = blockIdx.x % g.nbx, by = (blockIdx.x / g.nbx) % g.nby, b = blockIdx.x / (g.nbx * g.nby);
+  const int y0 = by * EV_TH, x0 = bx * EV_TW;
+  const int H = g.H, W = g.W, h = g.h;
+  const int64_t img = (int64_t)b * H * W;
+
+  for (int p = tid; p < PN; p += UN_THREADS) {
+    const int ly = p / PW, lx = p - ly * PW;
+    const int y = y0 - R + ly, x = x0 - R + lx;
+    const int64_t at = img + (int64_t)ev_reflect(y, H) * W + ev_reflect(x, W);
+    st[p] = g.src[at];
+    if (MU) z[p] = g.u0[at];
+    const bool inside = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+    gp[p] = inside ? g.gin[img + (int64_t)y * W + x] : 0.f;
+    gp[PN + p] = 0.f;
+  }
+  if (MU) {
+    for (int i = tid; i < EV_TH * EV_TW; i += UN_THREADS) {
+      const int y = y0 + i / EV_TW, x = x0 + i % EV_TW;
+      gzt[i] = (!g.first && y < H && x < W) ? g.gz[img + (int64_t)y * W + x] : 0.f;
+    }
+  }
+  __syncthreads();
+
+  // the h states again, as pde_evolve_kernel computes them
+  for (int s = 1; s <= h; ++s) {
+    const float* __restrict__ in = st + (s - 1) * PN;
+    float* __restrict__ out = st + s * PN;
+    const bool cl = CLAMP && s > 1;  // st[0] is a state, the later planes are pre-clamp
+    const int end = (PH - s) * PW - s;
+    for (int p = s * PW + s + tid; p < end; p += UN_THREADS) {
+      float c = in[p], up = in[p - PW], dn = in[p + PW], lf = in[p - 1], rt = in[p + 1];
+      if (cl) {
+        c = un_clamp(c); up = un_clamp(up); dn = un_clamp(dn); lf = un_clamp(lf); rt = un_clamp(rt);
+      }
+      float t = ev_mul(g.D, ev_lap(c, up, dn, lf, rt));
+      t = ev_add(t, ev_mul(g.k, ev_react(c, g.a)));
+      if (MU) t = ev_add(t, ev_mul(g.mu, ev_sub(z[p], c)));
+      out[p] = ev_add(c, ev_mul(g.dt, t));
+    }
+    __syncthreads();
+  }
+
+  int cur = 0;
+  for (int j = h - 1; j >= 0; --j) {
+    const float* __restrict__ nm = st + (j + 1) * PN;
+    const float* __restrict__ cj = st + j * PN;
+    const float* __restrict__ gi = gp + cur * PN;
+    float* __restrict__ go = gp + (cur ^ 1) * PN;
+    const int r = 2 * h - j;
+    const int end = (PH - r) * PW - r;
+    auto q_at = [&](int pp) -> float {
+      if (CLAMP) {
+        const float n = nm[pp];
+        if (n < 0.f || n > 1.f) return 0.f;
+      }
+      return gi[pp];
+    };
+    for (int p = r * PW + r + tid; p < end; p += UN_THREADS) {
+      const int ly = p / PW, lx = p - ly * PW;
+      const int y = y0 - R + ly, x = x0 - R + lx;
+      if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) continue;  // stays 0
+      const float wau = y == 0 ? 0.f : (y == 1 ? 2.f : 1.f), wbd = y == H - 1 ? 0.f : (y == H - 2 ? 2.f : 1.f);
+      const float wal = x == 0 ? 0.f : (x == 1 ? 2.f : 1.f), wbr = x == W - 1 ? 0.f : (x == W - 2 ? 2.f : 1.f);
+      const float q = q_at(p);
+      const float nb = ev_add(ev_add(ev_mul(wau, q_at(p - PW)), ev_mul(wbd, q_at(p + PW))),
+                              ev_add(ev_mul(wal, q_at(p - 1)), ev_mul(wbr, q_at(p + 1))));
+      float c = cj[p];
+      if (CLAMP && j > 0) c = un_clamp(c);
+      const float rp = ev_add(ev_mul(ev_sub(1.f, ev_mul(2.f, c)), ev_sub(c, g.a)), ev_mul(c, ev_sub(1.f, c)));
+      float s = ev_mul(g.k, rp);
+      s = ev_sub(s, g.fourD);
+      if (MU) s = ev_sub(s, g.mu);
+      const float d = ev_add(1.f, ev_mul(g.dt, s));
+      go[p] = ev_add(ev_mul(d, q), ev_mul(g.dtD, nb));
+      if (MU) {
+        const int ty = ly - R, tx = lx - R;
+        if ((unsigned)ty < (unsigned)EV_TH && (unsigned)tx < (unsigned)EV_TW)
+          gzt[ty * EV_TW + tx] = ev_add(gzt[ty * EV_TW + tx], ev_mul(g.dtmu, q));
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  const float* __restrict__ fin = gp + cur * PN;
+  for (int i = tid; i < EV_TH * EV_TW; i += UN_THREADS) {
+    const int ty = i / EV_TW, tx = i - ty * EV_TW;
+    const int y = y0 + ty, x = x0 + tx;
+    if (y >= H || x >= W) continue;
+    const int64_t at = img + (int64_t)y * W + x;
+    float v = fin[(R + ty) * PW + R + tx];
+    float zsum = 0.f;
+    if (MU) {
+      zsum = gzt[i];
+      g.gz[at] = zsum;
+    }
+    if (g.fold) v = ev_add(v, zsum);
+    g.gout[at] = v;
   }
 }
 
@@ -324,6 +476,194 @@ extern "C" int pis_pde_evolve(const float* u, const float* u0, float* out, uint8
     }
     if (int rc = launch_status("pde_evolve")) return rc;
     src = g.dst;
+  }
+  return PIS_OK;
+}
+
+// ---- unrolled evolution: checkpointed forward, reverse sweep --------------------------------------
+static int un_tb(int tb) {
+  if (tb == 0) tb = tune_get(PIS_TUNE_UNROLL_TB);
+  return (tb == 1 || tb == 2 || tb == 4) ? tb : 0;
+}
+
+extern "C" size_t pis_pde_unroll_ws(int B, int H, int W, int steps, int tb) {
+  const int T = un_tb(tb);
+  if (!ev_shape_ok(B, H, W) || steps < 0 || steps > PIS_UNROLL_MAX_STEPS || T == 0) {
+    set_error("pis_pde_unroll_ws: B >= 1, 2 <= H, W <= 4096, 0 <= steps <= %d and a temporal block of 1, 2 or 4 are needed",
+              PIS_UNROLL_MAX_STEPS);
+    return 0;
+  }
+  const int launches = steps == 0 ? 1 : (int)cdiv(steps, T);
+  return (size_t)(launches - 1) * ev_map_bytes(B, H, W);
+}
+
+extern "C" size_t pis_pde_unroll_bwd_ws(int B, int H, int W) {
+  if (!ev_shape_ok(B, H, W)) {
+    set_error("pis_pde_unroll_bwd_ws: B >= 1 and 2 <= H, W <= 4096 are needed");
+    return 0;
+  }
+  return 3 * ev_map_bytes(B, H, W);  // two gradient maps in turn, and the running sum when g_u0 is NULL
+}
+
+// the scalar checks of pis_pde_evolve
+static int un_check_scalars(const char* who, int B, int H, int W, float D, float k, float a, float mu, float dt, int steps,
+                            int flags) {
+  PIS_CHECK_ARG(ev_shape_ok(B, H, W), "%s: B = %d, H = %d, W = %d: B >= 1 and 2 <= H, W <= 4096 are needed", who, B, H, W);
+  PIS_CHECK_ARG(steps >= 0 && steps <= PIS_UNROLL_MAX_STEPS, "%s: steps = %d: [0, %d] is needed", who, steps,
+                PIS_UNROLL_MAX_STEPS);
+  PIS_CHECK_ARG((flags & ~PIS_EVOLVE_CLAMP) == 0, "%s: unknown flags 0x%x", who, flags);
+  PIS_CHECK_ARG(D >= 0.f && k >= 0.f && mu >= 0.f && a > 0.f && a < 1.f && dt > 0.f,
+                "%s: D >= 0, k >= 0, mu >= 0, 0 < a < 1 and dt > 0 are needed", who);
+  PIS_CHECK_ARG((double)dt * (4.0 * D + (double)k + (double)mu) <= 1.0,
+                "%s: dt (4 D + k + mu) = %g exceeds 1: the explicit step is not monotone", who,
+                (double)dt * (4.0 * D + (double)k + (double)mu));
+  return PIS_OK;
+}
+
+extern "C" int pis_pde_unroll_fwd(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B, int H,
+                                  int W, float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
+                                  pis_stream_t stream) {
+  PIS_CHECK_ARG(u && out, "pis_pde_unroll_fwd: u or out is NULL");
+  if (int rc = un_check_scalars("pis_pde_unroll_fwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+  const int T = un_tb(tb);
+  PIS_CHECK_ARG(T != 0, "pis_pde_unroll_fwd: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", tb,
+                PIS_TUNE_UNROLL_TB, tune_get(PIS_TUNE_UNROLL_TB));
+  PIS_CHECK_ARG(((uintptr_t)u | (uintptr_t)u0 | (uintptr_t)out | (uintptr_t)ckpt) % 16 == 0,
+                "pis_pde_unroll_fwd: u, u0, out and ckpt must be 16-byte aligned");
+  const size_t bytes = (size_t)B * H * W * sizeof(float), map = ev_map_bytes(B, H, W);
+  const int launches = steps == 0 ? 1 : (int)cdiv(steps, T);
+  const size_t need = (size_t)(launches - 1) * map;
+  PIS_CHECK_ARG(need == 0 || (ckpt && ckpt_bytes >= need),
+                "pis_pde_unroll_fwd: checkpoint stack missing or too small (%zu < %zu bytes)", ckpt_bytes, need);
+  PIS_CHECK_ARG(!ev_overlap(out, bytes, u, bytes) && !(u0 && ev_overlap(out, bytes, u0, bytes)) &&
+                    (!need || (!ev_overlap(ckpt, need, u, bytes) && !ev_overlap(ckpt, need, out, bytes) &&
+                               !(u0 && ev_overlap(ckpt, need, u0, bytes)))),
+                "pis_pde_unroll_fwd: out or ckpt overlaps another map");
+  EvolveArgs g{};
+  g.H = H; g.W = W;
+  g.nbx = (int)cdiv(W, EV_TW);
+  g.nby = (int)cdiv(H, EV_TH);
+  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt; g.thr = 0.f;
+  g.u0 = u0 ? u0 : u;
+  g.mask = nullptr;
+  const unsigned blocks = (unsigned)((int64_t)B * g.nbx * g.nby);
+  const bool with_mu = mu != 0.f, clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
+  const float* src = u;
+  for (int i = 0, left = steps; i < launches; ++i) {
+    g.src = src;
+    g.dst = i == launches - 1 ? out : (float*)((char*)ckpt + (size_t)i * map);  // slot i: the state after block i
+    g.h = std::min(left, T);
+    left -= g.h;
+    if (with_mu) {
+      if (clamp) ev_launch<true, true>(T, blocks, (hipStream_t)stream, g);
+      else ev_launch<true, false>(T, blocks, (hipStream_t)stream, g);
+    } else {
+      if (clamp) ev_launch<false, true>(T, blocks, (hipStream_t)stream, g);
+      else ev_launch<false, false>(T, blocks, (hipStream_t)stream, g);
+    }
+    if (int rc = launch_status("pde_unroll_fwd")) return rc;
+    src = g.dst;
+  }
+  return PIS_OK;
+}
+
+template <bool MU, bool CLAMP>
+static void un_launch(int T, unsigned blocks, hipStream_t s, const UnrollBwdArgs& a) {
+  switch (T) {
+    case 1:
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 1>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<1>(MU), s, a);
+      break;
+    case 2:
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 2>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<2>(MU), s, a);
+      break;
+    default:
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 4>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<4>(MU), s, a);
+      break;
+  }
+}
+static_assert(un_lds_bytes<4>(true) <= 160 * 1024, "the reverse sweep's planes must fit one workgroup's LDS");
+
+extern "C" int pis_pde_unroll_bwd(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
+                                  float* g_u0, int B, int H, int W, float D, float k, float a, float mu, float dt,
+                                  int steps, int flags, int tb, void* ws, size_t ws_bytes, pis_stream_t stream) {
+  PIS_CHECK_ARG(u && g_out && g_u, "pis_pde_unroll_bwd: u, g_out or g_u is NULL");
+  PIS_CHECK_ARG(u0 || !g_u0, "pis_pde_unroll_bwd: g_u0 without u0 (u is then its own u0 and g_u holds the sum)");
+  if (int rc = un_check_scalars("pis_pde_unroll_bwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+  const int T = un_tb(tb);
+  PIS_CHECK_ARG(T != 0, "pis_pde_unroll_bwd: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", tb,
+                PIS_TUNE_UNROLL_TB, tune_get(PIS_TUNE_UNROLL_TB));
+  PIS_CHECK_ARG(((uintptr_t)u | (uintptr_t)u0 | (uintptr_t)ckpt | (uintptr_t)g_out | (uintptr_t)g_u | (uintptr_t)g_u0 |
+                 (uintptr_t)ws) % 16 == 0,
+                "pis_pde_unroll_bwd: every map, ckpt and ws must be 16-byte aligned");
+  const size_t bytes = (size_t)B * H * W * sizeof(float), map = ev_map_bytes(B, H, W);
+  const int launches = steps == 0 ? 0 : (int)cdiv(steps, T);
+  const size_t stack = launches > 1 ? (size_t)(launches - 1) * map : 0;
+  PIS_CHECK_ARG(stack == 0 || ckpt, "pis_pde_unroll_bwd: ckpt is NULL (%d checkpoints are needed)", launches - 1);
+  const bool with_mu = mu != 0.f, clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
+  const bool carry_in_ws = with_mu && !g_u0;
+  const size_t need = steps == 0 ? 0 : (size_t)(std::min(launches - 1, 2)) * map;  // the gradient maps in turn
+  const size_t need_all = carry_in_ws ? 3 * map : need;                           // the running sum sits third
+  PIS_CHECK_ARG(need_all == 0 || (ws && ws_bytes >= need_all),
+                "pis_pde_unroll_bwd: workspace missing or too small (%zu < %zu bytes)", ws_bytes, need_all);
+  {
+    const void* p[7] = {g_u, g_u0, need_all ? ws : nullptr, g_out, u, u0, stack ? ckpt : nullptr};
+    const size_t n[7] = {bytes, bytes, need_all, bytes, bytes, bytes, stack};
+    // what is written (the first three) meets nothing; the inputs may meet each other (u0 may be u)
+    bool ok = true;
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 7; ++j)
+        ok = ok && !(p[i] && p[j] && n[i] && n[j] && ev_overlap(p[i], n[i], p[j], n[j]));
+    PIS_CHECK_ARG(ok, "pis_pde_unroll_bwd: g_u, g_u0 or ws overlaps another map");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if ((steps == 0 || !with_mu) && g_u0) {  // nothing reaches u0
+    const hipError_t e = hipMemsetAsync(g_u0, 0, bytes, s);
+    if (e != hipSuccess) {
+      set_error("pis_pde_unroll_bwd: clearing g_u0: %s", hipGetErrorString(e));
+      return PIS_ERR_LAUNCH;
+    }
+  }
+  if (steps == 0) {  // the identity
+    const hipError_t e = hipMemcpyAsync(g_u, g_out, bytes, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) {
+      set_error("pis_pde_unroll_bwd: copying g_out: %s", hipGetErrorString(e));
+      return PIS_ERR_LAUNCH;
+    }
+    return PIS_OK;
+  }
+  UnrollBwdArgs g{};
+  g.H = H; g.W = W;
+  g.nbx = (int)cdiv(W, EV_TW);
+  g.nby = (int)cdiv(H, EV_TH);
+  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt;
+  {
+    // float32 products formed once, each rounded on its own (volatile: no contraction, no folding in double)
+    volatile float four_d = 4.f * D, dt_d = dt * D, dt_mu = dt * mu;
+    g.fourD = four_d; g.dtD = dt_d; g.dtmu = dt_mu;
+  }
+  g.u0 = u0 ? u0 : u;
+  g.gz = with_mu ? (g_u0 ? g_u0 : (float*)((char*)ws + 2 * map)) : nullptr;
+  const unsigned blocks = (unsigned)((int64_t)B * g.nbx * g.nby);
+  float* scratch[2] = {(float*)ws, (float*)((char*)ws + map)};
+  const float* gin = g_out;
+  for (int t = 0; t < launches; ++t) {
+    const int i = launches - 1 - t;  // the temporal block, last first
+    const bool last = t == launches - 1;
+    g.src = i == 0 ? u : (const float*)((const char*)ckpt + (size_t)(i - 1) * map);
+    g.h = std::min(T, steps - i * T);
+    g.gin = gin;
+    g.gout = last ? g_u : scratch[t & 1];  // launch t reads scratch[(t - 1) & 1] (g_out for t == 0)
+    g.first = t == 0;
+    g.fold = last && !u0;
+    if (with_mu) {
+      if (clamp) un_launch<true, true>(T, blocks, s, g);
+      else un_launch<true, false>(T, blocks, s, g);
+    } else {
+      if (clamp) un_launch<false, true>(T, blocks, s, g);
+      else un_launch<false, false>(T, blocks, s, g);
+    }
+    if (int rc = launch_status("pde_unroll_bwd")) return rc;
+    gin = g.gout;
   }
   return PIS_OK;
 }

@@ -15,6 +15,11 @@ under ``u_t = D lap(u) + k u (1 - u) (u - a) + mu (u0 - u)`` by explicit Euler s
 residual, phase-field energy and interface pixel count (``pis_pde_energies``). ``evolve_np`` and
 ``energies_np`` are their definitions of record in float32 numpy, operation for operation; the
 kernels agree with them bit for bit (tests/test_evolve_gpu.py).
+
+The PDE as a layer: ``unroll`` is ``evolve`` with a backward (``pis_pde_unroll_fwd`` /
+``pis_pde_unroll_bwd``: checkpoints every Tb steps, one reverse launch per Tb steps), ``PDELayer`` and
+``RefinedModel`` wrap it for training, and ``unroll_vjp_np`` is the backward's definition of record,
+again agreeing bit for bit (tests/test_unroll_gpu.py).
 """
 from __future__ import annotations
 
@@ -37,6 +42,9 @@ EVOLVE_TILE = (_hip.PIS_EVOLVE_TILE_H, _hip.PIS_EVOLVE_TILE_W)
 EVOLVE_T_VALUES = (1, 2, 4, 8)
 EVOLVE_MAX_STEPS, EVOLVE_MAX_SIDE = _hip.PIS_EVOLVE_MAX_STEPS, 4096
 _f32 = np.float32
+# the legal temporal blocks Tb of pis_pde_unroll_fwd / _bwd and the bound on their step count
+UNROLL_TB_VALUES = (1, 2, 4)
+UNROLL_MAX_STEPS = _hip.PIS_UNROLL_MAX_STEPS
 
 
 def evolve_temporal_block(value: Optional[int] = None) -> int:
@@ -46,6 +54,16 @@ def evolve_temporal_block(value: Optional[int] = None) -> int:
     if value is not None and value not in EVOLVE_T_VALUES:
         raise ValueError(f"temporal block {value!r}: one of {EVOLVE_T_VALUES} is needed")
     return int(_hip.lib().pis_tune(_hip.PIS_TUNE_EVOLVE_T, -1 if value is None else int(value)))
+
+
+def unroll_temporal_block(value: Optional[int] = None) -> int:
+    """The steps one checkpoint of ``unroll`` spans and one reverse launch sweeps back (pis_tune key
+    ``PIS_TUNE_UNROLL_TB``); with ``value`` (one of ``UNROLL_TB_VALUES``) it is set, and the previous
+    value returned. Every value gives the same bits; a forward keeps the value it ran with for its
+    backward."""
+    if value is not None and value not in UNROLL_TB_VALUES:
+        raise ValueError(f"temporal block {value!r}: one of {UNROLL_TB_VALUES} is needed")
+    return int(_hip.lib().pis_tune(_hip.PIS_TUNE_UNROLL_TB, -1 if value is None else int(value)))
 
 
 def _check_evolve(steps, D, k, a, mu, dt) -> Tuple[int, np.float32, np.float32, np.float32, np.float32, np.float32]:
@@ -133,6 +151,107 @@ def evolve_np(u, steps: int, D, k, a, mu=0.0, dt=None, clamp: bool = True, u0=No
     return c.reshape(shape)
 
 
+def _check_unroll(steps, D, k, a, mu, dt):
+    """``_check_evolve`` under the smaller step bound of the checkpointed path."""
+    out = _check_evolve(steps, D, k, a, mu, dt)
+    if out[0] > UNROLL_MAX_STEPS:
+        raise ValueError(f"steps = {steps!r}: an integer in [0, {UNROLL_MAX_STEPS}] is needed (the checkpoint stack is "
+                         "bounded)")
+    return out
+
+
+def _adjoint_weights_np(n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The transpose of reflect padding along an axis of n >= 2 pixels: pixel i receives
+    ``wa[i] q[i - 1] + wb[i] q[i + 1]``. wa = 0, 2, 1, 1, ... from the start, wb the same from the end."""
+    wa, wb = np.ones(n, np.float32), np.ones(n, np.float32)
+    wa[1], wb[n - 2] = 2, 2  # before the zeros: n = 2 gives wa = [0, 2], wb = [2, 0]
+    wa[0], wb[n - 1] = 0, 0
+    return wa, wb
+
+
+def unroll_vjp_np(u, g_out, steps: int, D, k, a, mu=0.0, dt=None, clamp: bool = True, u0=None
+                  ) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """The definition of ``unroll``'s backward: the vector-Jacobian product of ``evolve_np`` (same
+    arguments, ``steps <= UNROLL_MAX_STEPS``) with ``g_out``, the gradient with respect to the evolved
+    map, in float32 with every operation rounded on its own. Returns ``(g_u, g_u0)``.
+
+    The forward steps are ``evolve_np``'s; with ``c`` a step's input and ``n = c + dt t`` its update
+    before the clamp, the reverse step takes ``g'`` (gradient w.r.t. the step's output) to ``g``::
+
+        pass = not (n < 0) and not (n > 1)        # clamp off: everywhere; equality passes, as torch.clamp
+        q    = pass ? g' : 0
+        nb   = (fu + fd) + (fl + fr)
+          fu = wa_H[y] q[y-1, x]     fd = wb_H[y] q[y+1, x]
+          fl = wa_W[x] q[y, x-1]     fr = wb_W[x] q[y, x+1]
+        rp   = ((1 - 2 c) (c - a)) + (c (1 - c))
+        s    = k rp;  s = s - (4 D);  if mu != 0: s = s - mu
+        d    = 1 + dt s
+        g    = d q + (dt D) nb
+        if mu != 0:  gz = gz + (dt mu) q          # one running float32 sum, in reverse step order
+
+    A ``q`` outside the image is 0; ``wa``, ``wb`` are the transpose of reflect padding
+    (``_adjoint_weights_np``); ``4 D``, ``dt D`` and ``dt mu`` are float32 products formed once. The
+    pairing ``(fu + fd) + (fl + fr)`` makes the product commute bit for bit with an H flip, a W flip
+    and a transpose, as the forward does. ``g_u0 = gz`` (zeros when ``mu == 0``). With ``u0=None``
+    the initial map is its own ``u0``: ``g_u + gz`` (one add, made for ``mu == 0`` too) and ``None``
+    are returned. ``steps == 0`` is the identity: ``g_out``'s bits, and zeros or ``None``."""
+    steps, D, k, a, mu, dt = _check_unroll(steps, D, k, a, mu, dt)
+    shape = np.shape(u)
+    c = _maps_np(u, "unroll_vjp_np").copy()
+    g = _maps_np(g_out, "unroll_vjp_np: g_out")
+    if g.shape != c.shape:
+        raise ValueError(f"unroll_vjp_np: g_out {g.shape} does not match u {c.shape}")
+    g = g.copy()
+    z = c if u0 is None else _maps_np(u0, "unroll_vjp_np: u0")
+    if z.shape != c.shape:
+        raise ValueError(f"unroll_vjp_np: u0 {z.shape} does not match u {c.shape}")
+    z = z.copy()
+    one, two, four, zero = _f32(1), _f32(2), _f32(4), _f32(0)
+    four_d, dt_d, dt_mu = four * D, dt * D, dt * mu
+    (wa_h, wb_h), (wa_w, wb_w) = _adjoint_weights_np(c.shape[1]), _adjoint_weights_np(c.shape[2])
+    wa_h, wb_h = wa_h[None, :, None], wb_h[None, :, None]
+    wa_w, wb_w = wa_w[None, None, :], wb_w[None, None, :]
+    states, passes = [], []
+    gz = np.zeros_like(c)
+    with np.errstate(all="ignore"):
+        for _ in range(steps):  # evolve_np's step, keeping its input and its pass mask
+            up, dn, lf, rt = _neighbours_np(c)
+            lap = ((up + dn) + (lf + rt)) - four * c
+            r = (c * (one - c)) * (c - a)
+            t = D * lap
+            t = t + k * r
+            if mu != 0:
+                t = t + mu * (z - c)
+            n = c + dt * t
+            states.append(c)
+            passes.append(~(n < zero) & ~(n > one) if clamp else None)
+            if clamp:
+                n = np.where(n < zero, zero, n)
+                n = np.where(n > one, one, n)
+            c = n.astype(np.float32, copy=False)
+        for c, ok in zip(reversed(states), reversed(passes)):
+            q = g if ok is None else np.where(ok, g, zero)
+            p = np.pad(q, ((0, 0), (1, 1), (1, 1)))
+            fu, fd = wa_h * p[:, :-2, 1:-1], wb_h * p[:, 2:, 1:-1]
+            fl, fr = wa_w * p[:, 1:-1, :-2], wb_w * p[:, 1:-1, 2:]
+            nb = (fu + fd) + (fl + fr)
+            rp = ((one - two * c) * (c - a)) + (c * (one - c))
+            s = k * rp
+            s = s - four_d
+            if mu != 0:
+                s = s - mu
+            d = one + dt * s
+            g = d * q + dt_d * nb
+            if mu != 0:
+                gz = gz + dt_mu * q
+            assert g.dtype == np.float32 and gz.dtype == np.float32
+    if steps == 0:
+        return g.reshape(shape), (None if u0 is None else gz.reshape(shape))
+    if u0 is None:
+        return (g + gz).reshape(shape), None
+    return g.reshape(shape), gz.reshape(shape)
+
+
 def energies_np(u, D, a, eps) -> Tuple[np.ndarray, np.ndarray]:
     """The definition of ``energies``: per image of float32 maps ``u``, ``(out (B, 2) float64,
     interface (B,) int64)`` with ``out[:, 0]`` the mean of ``double(res)^2``,
@@ -199,41 +318,73 @@ class PDERefine:
         return dict(steps=self.steps, D=self.D, k=self.k, a=self.a, mu=self.mu, dt=self.dt, clamp=self.clamp)
 
 
-def add_refine_flags(ap):
-    """--refine and its parameters on an argparse parser: shared by predict.py and evaluate.py."""
-    ap.add_argument("--refine", choices=["rd", "pf"], default=None,
-                    help="evolve the predicted probabilities under a PDE before the threshold: rd = the "
+def add_refine_flags(ap, prefix: str = "refine"):
+    """--refine and its parameters on an argparse parser: shared by predict.py and evaluate.py. With
+    ``prefix="pde-layer"`` the same set as --pde-layer, --pde-layer-steps, ...: the PDE layer of
+    training (main.py, run_ablation.py), whose steps are bounded by ``UNROLL_MAX_STEPS``."""
+    f = f"--{prefix}"
+    layer = prefix != "refine"
+    ap.add_argument(f, choices=["rd", "pf"], default=None,
+                    help=("train the PDE stage through K unrolled steps of a PDE on the predicted probabilities: "
+                          if layer else "evolve the predicted probabilities under a PDE before the threshold: ") +
+                         "rd = the "
                          "reaction-diffusion equation the loss penalises, pf = the Allen-Cahn flow of the "
                          "phase-field energy (default: off)")
-    ap.add_argument("--refine-steps", type=int, default=None, metavar="N",
-                    help="explicit time steps of --refine, 0..65536 (required with --refine)")
-    ap.add_argument("--refine-dt", type=float, default=None, metavar="F",
-                    help="time step of --refine (default: half the stability bound 1 / (4 D + k + mu))")
-    ap.add_argument("--refine-mu", type=float, default=0.0, metavar="F",
-                    help="fidelity weight of --refine: pulls the evolved map back to the prediction (default: 0)")
-    ap.add_argument("--refine-diffusion", type=float, default=1.0, metavar="F",
-                    help="diffusion coefficient of --refine rd (default: 1.0)")
-    ap.add_argument("--refine-threshold-a", type=float, default=0.5, metavar="F",
-                    help="reaction threshold a of --refine rd, in (0, 1) (default: 0.5)")
-    ap.add_argument("--refine-epsilon", type=float, default=0.05, metavar="F",
-                    help="interface width of --refine pf (default: 0.05)")
+    ap.add_argument(f"{f}-steps", type=int, default=None, metavar="N",
+                    help=f"explicit time steps of {f}, 0..{UNROLL_MAX_STEPS if layer else EVOLVE_MAX_STEPS} "
+                         f"(required with {f})")
+    ap.add_argument(f"{f}-dt", type=float, default=None, metavar="F",
+                    help=f"time step of {f} (default: half the stability bound 1 / (4 D + k + mu))")
+    ap.add_argument(f"{f}-mu", type=float, default=0.0, metavar="F",
+                    help=f"fidelity weight of {f}: pulls the evolved map back to the prediction (default: 0)")
+    ap.add_argument(f"{f}-diffusion", type=float, default=1.0, metavar="F",
+                    help=f"diffusion coefficient of {f} rd (default: 1.0)")
+    ap.add_argument(f"{f}-threshold-a", type=float, default=0.5, metavar="F",
+                    help=f"reaction threshold a of {f} rd, in (0, 1) (default: 0.5)")
+    ap.add_argument(f"{f}-epsilon", type=float, default=0.05, metavar="F",
+                    help=f"interface width of {f} pf (default: 0.05)")
 
 
-def refine_from_args(ap, args):
-    """The PDERefine of the parsed --refine flags, or None; a bad combination ends in ap.error."""
-    if args.refine is None:
-        if args.refine_steps is not None:
-            ap.error("--refine-steps needs --refine {rd,pf}")
+def refine_from_args(ap, args, prefix: str = "refine"):
+    """The PDERefine of the parsed --refine (or --``prefix``) flags, or None; a bad combination ends
+    in ap.error."""
+    f, dest = f"--{prefix}", prefix.replace("-", "_")
+    get = lambda name: getattr(args, f"{dest}_{name}")  # noqa: E731
+    kind, steps = getattr(args, dest), get("steps")
+    if kind is None:
+        if steps is not None:
+            ap.error(f"{f}-steps needs {f} {{rd,pf}}")
         return None
-    if args.refine_steps is None:
-        ap.error("--refine needs --refine-steps N")
+    if steps is None:
+        ap.error(f"{f} needs {f}-steps N")
     try:
-        if args.refine == "rd":
-            return PDERefine.reaction_diffusion(args.refine_steps, args.refine_diffusion, args.refine_threshold_a,
-                                                mu=args.refine_mu, dt=args.refine_dt)
-        return PDERefine.phase_field(args.refine_steps, args.refine_epsilon, mu=args.refine_mu, dt=args.refine_dt)
+        if prefix != "refine":
+            _check_unroll(steps, 0.0, 1.0, 0.5, 0.0, None)  # the step bound of the layer
+        if kind == "rd":
+            return PDERefine.reaction_diffusion(steps, get("diffusion"), get("threshold_a"), mu=get("mu"), dt=get("dt"))
+        return PDERefine.phase_field(steps, get("epsilon"), mu=get("mu"), dt=get("dt"))
     except ValueError as e:
-        ap.error(f"--refine: {e}")
+        ap.error(f"{f}: {e}")
+
+
+def refine_flags(refine: "PDERefine", kind: Optional[str] = None, prefix: str = "refine") -> str:
+    """The command-line flags (``add_refine_flags``) that rebuild ``refine``: as ``rd`` when
+    ``k == 1``, as ``pf`` when ``D = eps, k = 4 / eps, a = 1/2`` for some eps, unless ``kind`` says
+    which. Raises ValueError for a PDERefine neither preset gives."""
+    f = f"--{prefix}"
+    if kind is None:
+        kind = "rd" if refine.k == 1.0 else "pf"
+    if kind == "rd" and refine.k == 1.0:
+        out = f"{f} rd {f}-steps {refine.steps} {f}-diffusion {refine.D!r} {f}-threshold-a {refine.a!r}"
+    elif kind == "pf" and refine.D > 0 and refine.k == 4.0 / refine.D and refine.a == 0.5:
+        out = f"{f} pf {f}-steps {refine.steps} {f}-epsilon {refine.D!r}"
+    else:
+        raise ValueError(f"{refine}: neither the rd nor the pf preset")
+    if refine.mu:
+        out += f" {f}-mu {refine.mu!r}"
+    if refine.dt is not None:
+        out += f" {f}-dt {refine.dt!r}"
+    return out
 
 
 def _maps_cuda(u: torch.Tensor, what: str) -> torch.Tensor:
@@ -289,6 +440,113 @@ def evolve(u: torch.Tensor, refine: Optional[PDERefine] = None, *, steps: Option
                   _hip.stream_handle(uc.device))
     out = out.reshape(u.shape)
     return out if mask is None else (out, mask.reshape(u.shape))
+
+
+class _Unroll(torch.autograd.Function):
+    """``pis_pde_unroll_fwd`` and its reverse sweep ``pis_pde_unroll_bwd``; ``z`` is None when the
+    input is its own u0. The scalars are float32 already (``_check_unroll``)."""
+
+    @staticmethod
+    def forward(ctx, u, z, steps, D, k, a, mu, dt, clamp):
+        uc = _maps_cuda(u, "unroll")
+        zc = None if z is None else _maps_cuda(z, "unroll: u0")
+        B, H, W = uc.shape[0], uc.shape[-2], uc.shape[-1]
+        flags = _hip.PIS_EVOLVE_CLAMP if clamp else 0
+        f = ctypes.c_float
+        out = torch.empty_like(uc)
+        with torch.cuda.device(uc.device):
+            tb = int(_hip.lib().pis_tune(_hip.PIS_TUNE_UNROLL_TB, -1))  # read once: the backward runs with this one
+            nbytes = int(_hip.lib().pis_pde_unroll_ws(B, H, W, steps, tb))
+            ckpt = torch.empty(nbytes, dtype=torch.uint8, device=uc.device) if nbytes else None
+            _hip.call("pis_pde_unroll_fwd", _hip.ptr(uc), _hip.ptr(zc), _hip.ptr(out), _hip.ptr(ckpt), nbytes, B, H, W,
+                      f(D), f(k), f(a), f(mu), f(dt), steps, flags, tb, _hip.stream_handle(uc.device))
+        ctx.save_for_backward(uc, zc, ckpt)
+        ctx.args = (B, H, W, D, k, a, mu, dt, steps, flags, tb)
+        ctx.shapes = (u.shape, None if z is None else z.shape)
+        return out.reshape(u.shape)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        uc, zc, ckpt = ctx.saved_tensors
+        B, H, W, D, k, a, mu, dt, steps, flags, tb = ctx.args
+        if g_out.dtype != torch.float32:
+            raise TypeError(f"unroll: float32 gradient expected, got {g_out.dtype}")
+        g = g_out.contiguous()
+        g_u = torch.empty_like(uc)
+        g_z = torch.empty_like(uc) if zc is not None and ctx.needs_input_grad[1] else None
+        f = ctypes.c_float
+        with torch.cuda.device(uc.device):
+            nbytes = int(_hip.lib().pis_pde_unroll_bwd_ws(B, H, W))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=uc.device)
+            _hip.call("pis_pde_unroll_bwd", _hip.ptr(uc), _hip.ptr(zc), _hip.ptr(ckpt), _hip.ptr(g), _hip.ptr(g_u),
+                      _hip.ptr(g_z), B, H, W, f(D), f(k), f(a), f(mu), f(dt), steps, flags, tb, _hip.ptr(ws), nbytes,
+                      _hip.stream_handle(uc.device))
+        return (g_u.reshape(ctx.shapes[0]), None if g_z is None else g_z.reshape(ctx.shapes[1]),
+                None, None, None, None, None, None, None)
+
+
+def unroll(u: torch.Tensor, refine: Optional[PDERefine] = None, *, steps: Optional[int] = None, D=None, k=None,
+           a=None, mu=0.0, dt=None, clamp: bool = True, u0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``evolve`` as a differentiable layer: the same arguments without ``threshold``,
+    the same bits in the result, ``steps <= UNROLL_MAX_STEPS``, and gradients with respect to ``u``
+    and ``u0``: ``unroll_vjp_np`` on the GPU, bit for bit. The forward keeps the state after every
+    Tb-th step (``unroll_temporal_block``; ``ceil(steps / Tb) - 1`` maps beside ``u``), the backward
+    is one launch per block of Tb steps, last block first, each recomputing its states inside LDS.
+    With grad disabled, or when neither ``u`` nor ``u0`` requires grad, it is exactly one ``evolve``
+    call and keeps nothing. The PDE's coefficients take no gradient. No host synchronisation; bad
+    arguments raise ValueError before any GPU work."""
+    if refine is not None:
+        if not isinstance(refine, PDERefine):
+            raise TypeError(f"unroll: refine must be a PDERefine, got {type(refine).__name__}")
+        if steps is not None or D is not None or k is not None or a is not None:
+            raise ValueError("unroll: give a PDERefine or steps, D, k, a, not both")
+        steps, D, k, a, mu, dt, clamp = (refine.steps, refine.D, refine.k, refine.a, refine.mu, refine.dt,
+                                         refine.clamp)
+    elif steps is None or D is None or k is None or a is None:
+        raise ValueError("unroll: a PDERefine, or steps, D, k and a, are needed")
+    steps, D, k, a, mu, dt = _check_unroll(steps, D, k, a, mu, dt)
+    needs_grad = torch.is_grad_enabled() and (u.requires_grad or (u0 is not None and u0.requires_grad))
+    if not needs_grad:
+        return evolve(u, steps=steps, D=D, k=k, a=a, mu=mu, dt=dt, clamp=clamp, u0=u0)
+    _maps_cuda(u, "unroll")
+    if u0 is not None:
+        _maps_cuda(u0, "unroll: u0")
+        if u0.shape[0] != u.shape[0] or tuple(u0.shape[-2:]) != tuple(u.shape[-2:]) or u0.device != u.device:
+            raise ValueError(f"unroll: u0 {tuple(u0.shape)} does not match u {tuple(u.shape)}")
+    return _Unroll.apply(u, u0, steps, float(D), float(k), float(a), float(mu), float(dt), bool(clamp))
+
+
+class PDELayer(nn.Module):
+    """``unroll`` under a fixed ``PDERefine`` as a parameter-free module: ``forward(u) = unroll(u, refine)``."""
+
+    def __init__(self, refine: PDERefine):
+        super().__init__()
+        if not isinstance(refine, PDERefine):
+            raise TypeError(f"PDELayer: a PDERefine is needed, got {type(refine).__name__}")
+        _check_unroll(refine.steps, refine.D, refine.k, refine.a, refine.mu, refine.dt)
+        self.refine = refine
+
+    def forward(self, u: torch.Tensor) -> torch.Tensor:
+        return unroll(u, self.refine)
+
+    def extra_repr(self) -> str:
+        return repr(self.refine)
+
+
+class RefinedModel(nn.Module):
+    """``forward(x) = PDELayer(refine)(model(x))``: the network whose output is the evolved map, so a
+    loss on it reaches the weights through the unrolled steps. The U-Net stays reachable (and
+    checkpointed) as ``.model``. There is deliberately no ``forward_with_loss``: the training loop
+    then takes the two calls, the model and the criterion on the evolved map, and the fused
+    head + loss path is left only while the layer is on."""
+
+    def __init__(self, model: nn.Module, refine: PDERefine):
+        super().__init__()
+        self.model = model
+        self.layer = PDELayer(refine)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.layer(self.model(x))
 
 
 def energies(u: torch.Tensor, D=1.0, a=0.5, eps=0.05) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -414,4 +672,5 @@ def create_pde_regularization(diffusion_coeff: float = 1.0, reaction_threshold: 
 
 __all__ = ["PDERegularization", "create_pde_regularization", "PDERefine", "evolve", "evolve_np", "energies",
            "energies_np", "evolve_temporal_block", "EVOLVE_TILE", "EVOLVE_T_VALUES", "add_refine_flags",
-           "refine_from_args"]
+           "refine_from_args", "refine_flags", "unroll", "unroll_vjp_np", "unroll_temporal_block", "PDELayer",
+           "RefinedModel", "UNROLL_TB_VALUES", "UNROLL_MAX_STEPS"]

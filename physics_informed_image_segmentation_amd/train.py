@@ -493,7 +493,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
           num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
           augment=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
-          ema_decay: Optional[float] = None, ema_warmup: bool = True):
+          ema_decay: Optional[float] = None, ema_warmup: bool = True, pde_layer=None):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -519,9 +519,21 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     unchanged unet_baseline.pth / unet_pde_regularized.pth rank 0 writes unet_baseline_ema.pth /
     unet_pde_regularized_ema.pth (plain state dicts; the Stage-I comparison model loads the _ema
     file). Data parallel needs no communication for it: all ranks hold identical weights, hence
-    identical averages."""
+    identical averages.
+
+    ``pde_layer`` (a ``pde.PDERefine``, off by default): the PDE stage (Stage II, or the
+    single-stage PDE run) trains and validates ``pde.RefinedModel(model, pde_layer)``: the loss and
+    the Dice / IoU / boundary-F1 scores are taken on the map evolved by the unrolled steps, and the
+    gradient reaches the U-Net through them (the head and the loss then run as two calls). Stage I
+    is untouched. The checkpoints stay the inner U-Net's state dicts under the same names; that
+    stage's model is evaluated on the test set with ``refine=pde_layer``, and rank 0 writes the
+    layer's parameters to output/pde_layer_<stamp>.json and prints the ``predict.py --refine`` flags
+    that apply the same refinement at inference."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
+    if pde_layer is not None:
+        from .pde import PDELayer
+        PDELayer(pde_layer)  # TypeError / ValueError before any work
     rank, local_rank, world = init_from_env()
     if not torch.cuda.is_available():
         raise _hip.HipError("train(): the MI355X path needs a GPU (no CPU fallback in this build)")
@@ -581,14 +593,32 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         torch.cuda.manual_seed(seed + rank)
     grad_scale = 1.0 / world
 
-    def run(criterion, lr, epochs, name, csv_path):
+    def run(criterion, lr, epochs, name, csv_path, net=None):
         opt = AdamW(model.parameters(), lr=lr, weight_decay=1e-5, grad_scale=grad_scale,
                     max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
                     ema_warmup=ema_warmup)
         opts.append(opt)
         stopper = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
-        return train_stage(model, train_loader, val_loader, criterion, opt, device, num_epochs=epochs,
-                           stage_name=name, early_stopping=stopper, verbose=True, csv_path=csv_path)
+        return train_stage(model if net is None else net, train_loader, val_loader, criterion, opt, device,
+                           num_epochs=epochs, stage_name=name, early_stopping=stopper, verbose=True, csv_path=csv_path)
+
+    def pde_net():
+        """What the PDE stage trains: the U-Net, or the U-Net under the unrolled PDE layer."""
+        if pde_layer is None:
+            return None
+        from .pde import RefinedModel, refine_flags
+        say(f"  PDE layer: {pde_layer.steps} unrolled steps, D = {pde_layer.D}, k = {pde_layer.k}, a = {pde_layer.a}, "
+            f"mu = {pde_layer.mu}, dt = {pde_layer.dt}, clamp = {pde_layer.clamp}")
+        sidecar = out_dir / f"pde_layer_{stamp}.json"
+        if is_main:
+            with open(sidecar, "w") as fh:
+                json.dump(pde_layer.kwargs(), fh, indent=2)
+        say(f"  PDE layer parameters saved to: {sidecar}")
+        try:
+            say(f"  The same refinement at inference: predict.py {refine_flags(pde_layer)}")
+        except ValueError:
+            say("  The same refinement at inference: Predictor(refine=PDERefine(**<that file>))")
+        return RefinedModel(model, pde_layer)
 
     opts: List[AdamW] = []  # the stages' optimizers; the last one holds the final average
 
@@ -639,7 +669,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         lr2 = learning_rate * 0.1  # src/train.py:720
         say(f"  Learning rate for Stage II: {lr2:.2e} (reduced from {learning_rate:.2e})")
         csv2 = out_dir / f"metrics_stage2_{stamp}{frac}.csv"
-        best2, ep2, hist2 = run(pde_loss(), lr2, stage2_epochs, "Stage II", csv2)
+        best2, ep2, hist2 = run(pde_loss(), lr2, stage2_epochs, "Stage II", csv2, net=pde_net())
         result["stage2"] = (best2, ep2, hist2)
         if best2 and "val" in best2:
             say(f"\nStage II complete. Best validation Dice: {best2['val']['dice_score']:.6f} at epoch {ep2}")
@@ -656,7 +686,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         say("\n" + "=" * 70 + "\nSINGLE-STAGE TRAINING (PDE from start)\n" + "=" * 70)
         describe_pde()
         csv1s = out_dir / f"metrics_single_stage_{stamp}{frac}.csv"
-        best, ep, hist = run(pde_loss(), learning_rate, stage1_epochs, "Training", csv1s)
+        best, ep, hist = run(pde_loss(), learning_rate, stage1_epochs, "Training", csv1s, net=pde_net())
         result["single"] = (best, ep, hist)
         say(f"Single-stage metrics saved to: {csv1s}")
         final_path = models_dir / "unet_pde_regularized.pth"
@@ -673,7 +703,8 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         import contextlib
         with opts[-1].averaged_weights() if ema_decay is not None else contextlib.nullcontext():
             m = evaluate_on_test_set(model, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
-                                     model_name=name, device_cache=device_cache)
+                                     model_name=name, device_cache=device_cache,
+                                     **({} if pde_layer is None else {"refine": pde_layer}))
         tag = "stage2" if use_two_stage else "single_stage"
         save_test_metrics(m, out_dir / f"test_metrics_{tag}_{stamp}{frac}", model_name=name)
         result["test"] = m

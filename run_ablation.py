@@ -1,7 +1,9 @@
 """Ablation studies on the MI355X path — the CLI of the reference's run_ablation.py
 (run_ablation.py:297-470: same flags and defaults), plus ``--synthetic`` to train on the
 disc generator when the cell dataset is absent and ``--no-boundary-metrics`` to skip the
-host-side boundary F1 / Hausdorff.
+host-side boundary F1 / Hausdorff. ``--pde-layer {rd,pf} --pde-layer-steps N`` (with
+``--pde-layer-{dt,mu,diffusion,threshold-a,epsilon}``) trains every variant's PDE stage through the
+unrolled PDE layer (``pde.RefinedModel``).
 
     python run_ablation.py --ablation R1                       # BASELINE config C4
     python run_ablation.py --ablation S2 --synthetic 64 16 16 1024 1024   # C5 shape, synthetic
@@ -12,6 +14,7 @@ from pathlib import Path
 import torch
 
 from physics_informed_image_segmentation_amd.ablation import ABLATIONS, DataSpec, run_ablation_study
+from physics_informed_image_segmentation_amd.pde import add_refine_flags, refine_from_args
 
 
 def parse_args(argv=None):
@@ -52,7 +55,9 @@ def parse_args(argv=None):
                          "fused AdamW step; validation, early stopping and evaluation use it (default: off)")
     ap.add_argument("--no-ema-warmup", action="store_true",
                     help="use --ema-decay from the first step instead of min(decay, (1 + k) / (10 + k))")
+    add_refine_flags(ap, prefix="pde-layer")
     args = ap.parse_args(argv)
+    args.pde_layer_refine = refine_from_args(ap, args, prefix="pde-layer")
     if args.augment and not args.device_cache:
         ap.error("--augment needs --device-cache")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
@@ -87,7 +92,8 @@ def main(argv=None):
                                  num_workers=args.num_workers, boundary_metrics=not args.no_boundary_metrics,
                                  device_cache=args.device_cache, augment=args.augment,
                                  max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
-                                 ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
+                                 ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
+                                 **({} if args.pde_layer_refine is None else {"pde_layer": args.pde_layer_refine}))
         print(f"\nAblation {name} complete!\nResults: {res['results_json']}\nSummary: {res['summary_csv']}")
         out[name] = res
     print("\n" + "=" * 70 + "\nALL ABLATION STUDIES COMPLETE\n" + "=" * 70)
