@@ -285,7 +285,20 @@ int pis_version(void);
                                  ceil(steps / Tb) - 1 maps. A forward and its backward must use the same Tb: a
                                  caller that cannot rule out a change of the key in between reads it once and
                                  passes tb explicitly (pde.py does) */
-#define PIS_TUNE_NKEYS 58
+#define PIS_TUNE_WINO_WGRAD_TILE 58 /* pis_conv3x3_wgrad / _wgrad_keep, the Winograd weight gradient's batched GEMM
+                                 (csrc/wgrad.hip): the fp16x3 row-staged kernel on 256 x 128 block tiles
+                                 (wgrad_h3t_tile_kernel: 256 columns of E x 128 of V where Cout % 256 == 0, else
+                                 128 x 256; a K-step's 32 rows are staged once per tile). Contract: T = B (H/m)
+                                 (W/m) tiles with T % 32 == 0 and T >= 512, Cin and Cout multiples of 128 and one
+                                 of them of 256, keys 14 >= 2 and 31 != 0, 16-byte aligned operands. 0: never (the
+                                 128 x 128 kernels and bf16x6, as every shape outside the contract); 1 (default):
+                                 the shapes the planner's measured rule names (csrc/conv3x3_plan.hip
+                                 wino_tile_adopted); 2: every shape in the contract, on the
+                                 plan's split count; 3: every shape, the splits trimmed to one resident generation
+                                 of blocks. The key may change between any two calls: pis_conv3x3_wgrad_ws does not
+                                 depend on it (the tile form writes its slabs into the regions the 128 x 128 plan
+                                 sizes, with no more splits) */
+#define PIS_TUNE_NKEYS 59
 #define PIS_DEBUG_NOLOAD (1 << 16)
 int pis_tune(int key, int value);
 /* Tooling (tools/bench_gemm.py): time one batched NT GEMM kernel variant in isolation,
@@ -459,6 +472,15 @@ int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float
 /* Tooling and tests: the number of split-K slabs of the 256 x 128 tile plan (PIS_TUNE_CONVT_WGRAD_TILE) at this
  * shape, 0 where the shape is outside that kernel's contract. */
 int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout);
+/* Tooling and tests (host only, no GPU): the split-K kernel the Winograd weight gradient of pis_conv3x3_wgrad
+ * launches for this layer under the current keys, `aligned`: x and dz (and a kept transform) 16-byte aligned.
+ * -1: the layer's weight gradient is not a Winograd one (direct, halo, ...). Else bits 0..3: 0 fp32 MFMA,
+ * 1 bf16x6, 2 fp16x3 column-staged, 3 / 4 fp16x3 row-staged 128 x 128 (4: whole K-steps, buffer loads),
+ * 5 its timing twin, 6 the 256 x 128 tile kernel (PIS_TUNE_WINO_WGRAD_TILE), then bits 4..5: 1 the wide operand
+ * is E (output channels), 2 V (input channels). _plan also stores the launch's split count and its blocks
+ * (tiles x splits x transform planes) where the pointers are not NULL. */
+int pis_debug_wino_wgrad_kernel(int B, int H, int W, int Cin, int Cout, int aligned);
+int pis_debug_wino_wgrad_plan(int B, int H, int W, int Cin, int Cout, int aligned, int* splits, int* blocks);
 /* Tooling and tests: the algorithm the planner (csrc/convt_plan.h) resolves for a call of this shape under the
  * current keys. op 0: pis_convt2x2_fwd with ld_src = ldx, ld_dst = ldy and a bias; op 1: pis_convt2x2_dgrad with
  * ld_src = lddy, ld_dst = lddx = ldm and PIS_MASK; op 2: pis_convt2x2_wgrad with ld_src = ldx, ld_dst = lddy.

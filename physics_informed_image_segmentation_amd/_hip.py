@@ -26,6 +26,7 @@ PIS_TUNE_EVOLVE_T = 54  # include/pis_capi.h: steps per launch of pis_pde_evolve
 PIS_TUNE_EDT_PRUNE = 55  # include/pis_capi.h: what the distance transform's outward search skips (0, 1 or 3)
 PIS_TUNE_CONVT_WGRAD_TILE = 56  # include/pis_capi.h: transposed-conv weight gradient on 256 x 128 tiles (1) or the older kernels (0)
 PIS_TUNE_UNROLL_TB = 57  # include/pis_capi.h: steps per checkpoint and per reverse launch of pis_pde_unroll_* (1, 2 or 4)
+PIS_TUNE_WINO_WGRAD_TILE = 58  # include/pis_capi.h: Winograd weight-gradient GEMM on 256 x 128 tiles (0 never, 1 measured shapes, 2 / 3 forced)
 PIS_UNROLL_MAX_STEPS = 1024
 PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
@@ -87,6 +88,8 @@ _SIGNATURES = {
     "pis_convt2x2_wgrad": ([P, I, P, I, P, P, I, I, I, I, I, I, P, Z, P], c_int),
     "pis_debug_convt2x2_wgrad_tile_splits": ([I, I, I, I, I], c_int),
     "pis_debug_convt2x2_algo": ([I, I, I, I, I, I, I, I, I], c_int),
+    "pis_debug_wino_wgrad_kernel": ([I, I, I, I, I, I], c_int),
+    "pis_debug_wino_wgrad_plan": ([I, I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
     "pis_maxpool2x2_fwd": ([P, I, P, I, I, I, I, P], c_int),
     "pis_maxpool2x2_bwd": ([P, I, P, P, I, P, I, I, I, I, I, P], c_int),
     "pis_head_fwd": ([P, I, P, P, P, P, L, I, P], c_int),

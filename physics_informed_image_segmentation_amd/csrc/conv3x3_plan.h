@@ -25,6 +25,7 @@ enum class WgradKernel {
   H3T,        // wgrad_h3t_kernel: fp16x3, operands staged by rows, 128 x 128 tiles
   H3T_EXACT,  // ... its form for whole K-steps and 31-bit row offsets (h3t_exact)
   H3T_TWIN,   // ... its timing twin (pis_tune key 2, wrong results)
+  H3T_TILE,   // wgrad_h3t_tile_kernel: the Winograd weight gradient on 256 x 128 (bm = 256) or 128 x 256 tiles
 };
 constexpr int WT_BK = 32;  // pixels per K-step of the row-staged kernels
 // what the choice needs to know about a launch's operands A (rows lda) and B (rows ldb)
@@ -39,8 +40,11 @@ struct WgradOperands {
 // wgrad_h3t_kernel's EX form: whole K-steps in every split and 31-bit row offsets for the buffer
 // loads (the batch offsets go into the base pointers)
 bool h3t_exact(const WgradPlan& pl, const WgradOperands& o);
-// pis_tune keys 14 (arithmetic), 31 (row staging) and 2 (timing twins)
-WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o);
+// pis_tune keys 14 (arithmetic), 31 (row staging) and 2 (timing twins). `tile`: the launch's
+// 256 x 128 candidate (WinoWgradPlan::tile; bm == 0: none), taken (H3T_TILE, to be launched on
+// *tile, not pl) where the keys allow fp16x3 row staging and the operands meet its contract:
+// 16-byte aligned, lda / ldb / bs_a / bs_b multiples of 4, h3t_exact
+WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o, const WgradPlan* tile = nullptr);
 
 struct HaloPlan {
   bool use;
@@ -58,6 +62,10 @@ struct WinoWgradPlan {
   int m, nxi;
   int64_t T;
   WgradPlan gemm;
+  // pis_tune key 58: the same GEMMs on wgrad_h3t_tile_kernel's tile, where the shape is in its
+  // contract and (key = 1) in the measured set; bm == 0 otherwise. It lives in gemm's workspace
+  // regions: the same slab pitch, splits <= gemm.splits, pps a multiple of 32.
+  WgradPlan tile;
   size_t off_E, off_part, off_M, off_cs, total;
 };
 

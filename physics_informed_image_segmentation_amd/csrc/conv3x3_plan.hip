@@ -88,6 +88,55 @@ HaloPlan halo_plan(int B, int H, int W, int Cin, int Cout) {
   return p;
 }
 
+// pis_tune key 58: the Winograd weight gradient's GEMMs on wgrad_h3t_tile_kernel's 256 x 128 tile,
+// inside the split-K layout of p.gemm (the workspace is sized from p.gemm alone and never depends
+// on the key). Shape contract: T >= 512 in whole 32-row K-steps, both channel counts multiples of
+// 128 and one of 256; the wide operand is E (output channels) where Cout % 256 == 0, else V.
+// Key values: 0 never; 1 the measured set (wino_tile_adopted), on trimmed splits; 2 every shape in
+// the contract on p.gemm's splits; 3 every shape, with the splits trimmed to one resident generation.
+constexpr int WINO_TILE_RESIDENT = 512;  // blocks: two per CU
+
+// key 58 = 1: the shapes where the tile form's isolated time (GEMM + output transform, minimum of
+// three interleaved runs) beat the 128 x 128 form's by more than the latter's spread (DESIGN.md §4
+// round 11, profiles/wino_wgrad_tile_ab.txt), always on the trimmed split count where one exists.
+// Measured at batch 8 of 512^2 (GEMM + output transform, ms, 128 x 128 form -> tile form):
+//   one side a single 128-column tile: 128 x 256 channels at T = 32768 0.387 -> 0.340, 256 x 128
+//     at T = 8192 (bf16x6 before) 0.196 -> 0.112
+//   splits trimmed to one generation: 256 x 512 at T = 8192 0.384 -> 0.319 (untrimmed 0.382: no
+//     gain), 512 x 256 at T = 2048 0.121 -> 0.100
+//   512 x 512: T = 2048 0.207 -> 0.204, T = 512 0.072 -> 0.069 (small, but beyond the spread)
+// and not: 256 x 256 at T = 8192 (0.189 -> 0.176, inside the old form's spread of 0.041) and
+// 512 x 1024 at T = 2048 (0.374 -> 0.371, 576 blocks that cannot be trimmed: one split). Shapes of
+// neither kind keep the 128 x 128 form.
+bool wino_tile_adopted(int Cin, int Cout, bool trimmed) {
+  return std::min(Cin, Cout) == 128 || trimmed || (Cin == Cout && Cin >= 512);
+}
+
+WgradPlan wino_tile_plan(const WinoWgradPlan& p, int Cin, int Cout) {
+  WgradPlan t{};
+  const int key = tune_get(PIS_TUNE_WINO_WGRAD_TILE);
+  if (key == 0 || p.T % WT_BK || p.T < 512 || Cin % 128 || Cout % 128 || (Cin % 256 && Cout % 256)) return t;
+  const bool trim = key != 2;
+  bool trimmed = false;
+  t = p.gemm;  // pps: a multiple of 64
+  t.bm = Cout % 256 == 0 ? 256 : 128;
+  t.bn = Cout % 256 == 0 ? 128 : 256;
+  const int tiles = (Cout / t.bm) * (Cin / t.bn);
+  // a generation and an eighth (576 blocks where the 128 x 128 plan made 1152) runs as two: fewer,
+  // longer splits that fit one, where at least two remain
+  const int fit = WINO_TILE_RESIDENT / (tiles * p.nxi);
+  if (trim && t.splits > 1 && tiles * t.splits * p.nxi > WINO_TILE_RESIDENT && fit >= 2) {
+    const int64_t pps = cdiv(cdiv(p.T, (int64_t)fit), WT_BK) * WT_BK;
+    if (pps <= 8192) {  // plan_wgrad's bound on an fp32 chain
+      t.pps = (int)pps;
+      t.splits = (int)cdiv(p.T, pps);
+      trimmed = true;
+    }
+  }
+  if (key == 1 && !wino_tile_adopted(Cin, Cout, trimmed)) return WgradPlan{};
+  return t;
+}
+
 WinoWgradPlan wino_wgrad_plan(int B, int H, int W, int Cin, int Cout) {
   WinoWgradPlan p{};
   const int mode = tune_get(PIS_TUNE_WINOGRAD);
@@ -104,6 +153,7 @@ WinoWgradPlan wino_wgrad_plan(int B, int H, int W, int Cin, int Cout) {
   p.T = (int64_t)B * (H / p.m) * (W / p.m);
   // the nxi GEMMs share one launch: split so all of them together make ~target blocks
   p.gemm = plan_wgrad(Cout, Cin, (int)p.T, Cout, Cin, std::max(16, tune_get(PIS_TUNE_WINO_WGRAD_BLOCKS) / p.nxi));
+  p.tile = wino_tile_plan(p, Cin, Cout);
   auto al = [](size_t b) { return cdiv(b, 256) * 256; };
   const size_t V = al((size_t)p.nxi * p.T * Cin * 4), E = al((size_t)p.nxi * p.T * Cout * 4);
   const size_t part = al((size_t)p.gemm.splits * p.nxi * Cout * Cin * 4), M = al((size_t)p.nxi * Cout * Cin * 4);
@@ -179,7 +229,14 @@ bool h3t_exact(const WgradPlan& pl, const WgradOperands& o) {
          ((int64_t)o.P + WT_BK) * std::max(o.a_up2 ? 0 : o.lda, o.ldb) * 4 < (int64_t(1) << 31);
 }
 
-WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o) {
+WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o, const WgradPlan* tile) {
+  // the Winograd weight gradient's 256 x 128 tile candidate (key 58, wino_tile_plan): fp16x3 row
+  // staging allowed by keys 14 and 31 (at key 14 = 3 also the 128-input-channel layer that else
+  // runs bf16x6), no timing twin, and the operand contract of its float4 buffer loads
+  if (tile && tile->bm != 0 && o.plain && !o.a_up2 && tune_get(PIS_TUNE_WGRAD_X6) >= 2 && tune_get(PIS_TUNE_WGRAD_T) != 0 &&
+      tune_get(PIS_TUNE_DEBUG_NOLOAD) == 0 && o.lda % 4 == 0 && o.ldb % 4 == 0 && o.bs_a % 4 == 0 && o.bs_b % 4 == 0 &&
+      o.aligned16 && h3t_exact(*tile, o))
+    return WgradKernel::H3T_TILE;
   // key 14 = 3 (auto): fp16x3 where the layer has >= 256 input channels. The bf16x6
   // and fp16x3 kernels take plain B operands only, where Np IS the input-channel count (Winograd:
   // Cin; convT: Cin); the 3x3 conv's gathered operand (Np = 9 Cin) runs the fp32 MFMA kernel. Their
@@ -302,3 +359,26 @@ WgradAlgo resolve_wgrad(const Conv3x3Plan& p, const void* x, const void* dz, siz
 }
 
 }  // namespace pis
+
+using namespace pis;
+
+extern "C" int pis_debug_wino_wgrad_plan(int B, int H, int W, int Cin, int Cout, int aligned, int* splits, int* blocks) {
+  if (splits) *splits = 0;
+  if (blocks) *blocks = 0;
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
+  const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
+  const WgradAlgo algo = (p.wgrad == WGRAD_DIRECT && aligned) ? WGRAD_DIRECT : p.wgrad_nodirect;
+  if (algo != WGRAD_WINO4 && algo != WGRAD_WINO2) return -1;
+  const WinoWgradPlan& w = p.wino_w;
+  // wino_wgrad's operands: E[xi][T][Cout] and V[xi][T][Cin]
+  const WgradOperands o{true, false, (int)w.T, (int)w.T, Cin, Cout, Cin, w.T * Cout, w.T * Cin, aligned != 0};
+  const WgradKernel k = choose_wgrad_kernel(w.gemm, o, &w.tile);
+  const WgradPlan& pl = k == WgradKernel::H3T_TILE ? w.tile : w.gemm;
+  if (splits) *splits = pl.splits;
+  if (blocks) *blocks = (Cout / pl.bm) * (Cin / pl.bn) * pl.splits * w.nxi;
+  return (int)k | (k == WgradKernel::H3T_TILE ? (pl.bm == 256 ? 1 : 2) << 4 : 0);
+}
+
+extern "C" int pis_debug_wino_wgrad_kernel(int B, int H, int W, int Cin, int Cout, int aligned) {
+  return pis_debug_wino_wgrad_plan(B, H, W, Cin, Cout, aligned, nullptr, nullptr);
+}

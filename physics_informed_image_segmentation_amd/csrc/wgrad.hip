@@ -1011,9 +1011,10 @@ constexpr int WT_BUF = 4 * WT_PLANE;             // A hi, A lo, B hi, B lo
 
 __device__ __forceinline__ int wtsw(int row, int chunk) { return row * 128 + 8 * (chunk ^ ((row & 3) << 2)); }
 
-// ---- pieces shared by the two row-staged kernels (wgrad_h3t_kernel, wgrad_up2_tile_kernel) ----
+// ---- pieces shared by the row-staged kernels (wgrad_h3t_kernel, wgrad_up2_tile_kernel,
+// wgrad_h3t_tile_kernel) ----
 // (their transposed fragment read, accumulator re-expression and slab epilogue stay written out in
-// both: as shared functions they changed the kernels' code, profiles/convt_plan_codegen.txt)
+// each: as shared functions they changed the kernels' code, profiles/convt_plan_codegen.txt)
 __device__ __forceinline__ float umax4(const float (&r)[4]) {  // r >= 0: bit-pattern max
   return __uint_as_float(max(max(__float_as_uint(r[0]), __float_as_uint(r[1])),
                              max(__float_as_uint(r[2]), __float_as_uint(r[3]))));
@@ -1481,6 +1482,224 @@ __global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
   }
 }
 
+// The Winograd weight gradient on 256 x 128 tiles (pis_tune key 58): wgrad_up2_tile_kernel's form
+// for the plain operands A = E[xi][T][Cout], B = V[xi][T][Cin] of the batched launch (one batch
+// per xi, xcd_remap2). Same arithmetic as wgrad_h3t_kernel: fp16x3, smallest products first, one
+// power-of-two scale per operand and K-step of 32 rows from the block-wide max (h3_keep), the
+// accumulator units kept as two factors. The block tile is 256 columns of one operand x 128 of
+// the other, so a K-step's rows of the narrow operand are staged once per 256 columns of the wide
+// one (the 128 x 128 form: once per 128), and a wave's 128 x 64 sub-tile (4 x 2 accumulator
+// blocks) reads 24 transposed fragments per 48 MFMAs instead of 16 per 24.
+// WB = false: the wide operand is A (Cout % 256 == 0); wave (w0, w1) owns output channels
+// 128 w0 .. x input channels 64 w1 ... WB = true: the wide operand is B (Cout = 128 against
+// Cin % 256 == 0); wave (w0, w1) owns output channels 64 w1 .. x input channels 128 w0 ... Either
+// way A is the MFMA's row operand, so a slab store's 32 lanes run along Cin (128 contiguous bytes).
+// LDS: one K-step, six [32][128] planes (wtsw): A hi, A lo, B hi, B lo with two planes for each of
+// the wide operand's = 48 KB, two blocks per CU; two barriers per K-step; the raw operands of
+// K-step st + 1 are loaded (buffer loads from the block's base, whole K-steps: h3t_exact) while
+// K-step st multiplies. Slabs at part + split * split_stride (+ xi Cout Cin in the base), bias
+// partials [split][Cout] by the blocks of plane bias_xi whose Cin tile is the first. No atomics.
+template <bool WB>
+__global__ __launch_bounds__(256, 2) void wgrad_h3t_tile_kernel(WgradArgs g) {
+  const Remap2 rm = xcd_remap2();
+  if (rm.batch) {
+    g.a += rm.batch * g.bs_a;
+    g.b += rm.batch * g.bs_b;
+    g.part += rm.batch * g.bs_part;
+  }
+  constexpr int BMT = WB ? 128 : 256, BNT = WB ? 256 : 128;  // block tile
+  constexpr int HA = WB ? 1 : 2, HB = WB ? 2 : 1;            // 128-column halves of A, of B
+  constexpr int NA = WB ? 2 : 4, NB = WB ? 4 : 2;            // a wave's 32 x 32 accumulator blocks
+  __shared__ __attribute__((aligned(16))) _Float16 smem[WU_LDS];
+  __shared__ float red[2][2][4];  // [K-step parity][A|B][wave] maxima
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int w0 = wave & 1, w1 = wave >> 1, li = lane & 31, lh = lane >> 5;
+  const int ntn = g.Np / BNT;
+  const int tiles = (g.Mp / BMT) * ntn;
+  const int bid = rm.bid;
+  const int split = bid / tiles;
+  const int tile = bid - split * tiles;
+  const int m0 = (tile / ntn) * BMT, n0 = (tile % ntn) * BNT;
+  const int p_begin = split * g.pix_per_split;
+  const int p_end = min(g.P, p_begin + g.pix_per_split);
+  const int nst = max(0, (p_end - p_begin) / WT_BK);
+  // staging: rows srow + 8 j, float4 column sc4 of each 128-column half
+  const int srow = tid >> 5, sc4 = tid & 31;
+  const bool do_bias = g.part_bias != nullptr && n0 == 0 && rm.batch == g.bias_xi;
+  f32x4 bsum[HA];
+#pragma unroll
+  for (int h = 0; h < HA; ++h) bsum[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // buffer resources at the block's column bases; lane offsets of row p_begin + srow
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.a + m0), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.b + n0), (short)0, 0x7fffffff, 0x00020000);
+  const uint32_t la0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.lda + 4u * sc4);
+  const uint32_t lb0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.ldb + 4u * sc4);
+  f32x4 xa[HA][4], xb[HB][4];
+  auto gload = [&](int st) __attribute__((always_inline)) {  // rows p_begin + 32 st + srow + 8 j, all inside the split
+    const uint32_t ra_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.lda, rb_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.ldb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int h = 0; h < HA; ++h)
+        xa[h][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsa, la0, ra_s + 4u * (uint32_t)(8 * j) * (uint32_t)g.lda + 512u * h, 0));
+#pragma unroll
+      for (int h = 0; h < HB; ++h)
+        xb[h][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsb, lb0, rb_s + 4u * (uint32_t)(8 * j) * (uint32_t)g.ldb + 512u * h, 0));
+    }
+  };
+  auto publish = [&](int par) __attribute__((always_inline)) {
+    if (do_bias) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int h = 0; h < HA; ++h) bsum[h] += xa[h][j];
+    }
+    const float ma = wave_max_nonneg(absmax_x4(xa));
+    const float mb = wave_max_nonneg(absmax_x4(xb));
+    if (lane == 0) {
+      red[par][0][wave] = ma;
+      red[par][1][wave] = mb;
+    }
+  };
+  // planes: A hi [HA], A lo [HA], B hi [HB], B lo [HB]
+  float sa = 0.f, sb = 0.f, sa_min = __builtin_inff(), sb_min = __builtin_inff();  // the staged K-step's scales
+  auto split_store = [&](int par) __attribute__((always_inline)) {
+    sa = h3_keep(sa, umax4(red[par][0]), sa_min);
+    sb = h3_keep(sb, umax4(red[par][1]), sb_min);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int off = wtsw(srow + 8 * j, sc4 >> 1) + 4 * (sc4 & 1);
+      u32x2 h, l;
+#pragma unroll
+      for (int hf = 0; hf < HA; ++hf) {
+        split2h_x4(xa[hf][j] * sa, h, l);
+        *reinterpret_cast<u32x2*>(smem + hf * WT_PLANE + off) = h;
+        *reinterpret_cast<u32x2*>(smem + (HA + hf) * WT_PLANE + off) = l;
+      }
+#pragma unroll
+      for (int hf = 0; hf < HB; ++hf) {
+        split2h_x4(xb[hf][j] * sb, h, l);
+        *reinterpret_cast<u32x2*>(smem + (2 * HA + hf) * WT_PLANE + off) = h;
+        *reinterpret_cast<u32x2*>(smem + (2 * HA + HB + hf) * WT_PLANE + off) = l;
+      }
+    }
+  };
+
+  // transposed-read lane roles, as wgrad_h3t_kernel
+  const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const int kh = gq >> 1, chk = 2 * (gq & 1) + (pp >> 1), slot = 4 * (pp & 1);
+  auto frag = [&](const _Float16* plane, int ks, int col0) __attribute__((always_inline)) {
+    const int row = 16 * ks + 8 * kh + q, ch = col0 / 8 + chk;
+    const s16x4 lo4 = tr_read(plane + wtsw(row, ch) + slot);
+    const s16x4 hi4 = tr_read(plane + wtsw(row + 4, ch) + slot);
+    return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+  };
+  // this wave's plane of each operand and its first column there
+  const _Float16* a_hi = smem + (WB ? 0 : w0) * WT_PLANE;
+  const _Float16* a_lo = a_hi + HA * WT_PLANE;
+  const _Float16* b_hi = smem + (2 * HA + (WB ? w0 : 0)) * WT_PLANE;
+  const _Float16* b_lo = b_hi + HB * WT_PLANE;
+  const int ca0 = WB ? 64 * w1 : 0, cb0 = WB ? 0 : 64 * w1;
+
+  f32x16 acc[NA][NB];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  // the partial sums are in units ua * ub, kept as two factors (0: none yet), as wgrad_h3t_kernel
+  float ua = 0.f, ub = 0.f;
+
+  if (nst > 0) {
+    gload(0);
+    publish(0);
+    __syncthreads();
+    split_store(0);
+    if (nst > 1) gload(1);
+  }
+#pragma unroll 1
+  for (int st = 0; st < nst; ++st) {
+    __syncthreads();  // K-step st staged
+    if (sa != ua || sb != ub) {  // the partial sums in this K-step's units (exact: powers of two)
+      if (ua != 0.f) {
+        const float fa = sa / ua, fb = sb / ub;
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+          for (int b = 0; b < NB; ++b) acc[a][b] = (acc[a][b] * fa) * fb;
+      }
+      ua = sa;
+      ub = sb;
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      if constexpr (!WB) {  // the narrow operand's fragments held, the wide one's streamed
+        f16x8 bf[2][NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          bf[0][b] = frag(b_hi, ks, cb0 + 32 * b);
+          bf[1][b] = frag(b_lo, ks, cb0 + 32 * b);
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          const f16x8 ah = frag(a_hi, ks, ca0 + 32 * a), al = frag(a_lo, ks, ca0 + 32 * a);
+#pragma unroll
+          for (int b = 0; b < NB; ++b) acc[a][b] = h3_mfma3(ah, al, bf[0][b], bf[1][b], acc[a][b]);
+        }
+      } else {
+        f16x8 af[2][NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          af[0][a] = frag(a_hi, ks, ca0 + 32 * a);
+          af[1][a] = frag(a_lo, ks, ca0 + 32 * a);
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const f16x8 bh = frag(b_hi, ks, cb0 + 32 * b), bl = frag(b_lo, ks, cb0 + 32 * b);
+#pragma unroll
+          for (int a = 0; a < NA; ++a) acc[a][b] = h3_mfma3(af[0][a], af[1][a], bh, bl, acc[a][b]);
+        }
+      }
+    }
+    const bool more = st + 1 < nst;
+    if (more) publish((st + 1) & 1);
+    __syncthreads();  // every wave has read K-step st's fragments
+    if (more) {
+      split_store((st + 1) & 1);
+      if (st + 2 < nst) gload(st + 2);
+    }
+  }
+  float* out = g.part + (size_t)split * (g.split_stride ? g.split_stride : (int64_t)g.Mp * g.Np);
+  const float inv_a = ua != 0.f ? 1.f / ua : 0.f, inv_b = ub != 0.f ? 1.f / ub : 0.f;
+  const int mw = m0 + (WB ? 64 * w1 : 128 * w0), nw = n0 + (WB ? 128 * w0 : 64 * w1);
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int n = nw + 32 * b + li;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = mw + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        out[(size_t)m * g.Np + n] = (acc[a][b][r] * inv_a) * inv_b;
+      }
+    }
+  if (do_bias) {  // column sums of the raw E rows: the 8 threads of each column group, fixed order
+    f32x4* rb4 = reinterpret_cast<f32x4*>(smem);  // the loop's last barrier is behind every fragment read
+#pragma unroll
+    for (int h = 0; h < HA; ++h) rb4[256 * h + tid] = bsum[h];
+    __syncthreads();
+    if (tid < 32 * HA) {
+      const int base = 256 * (tid >> 5) + (tid & 31);
+      f32x4 t = rb4[base];
+#pragma unroll
+      for (int r = 1; r < 8; ++r) t += rb4[base + 32 * r];
+      *reinterpret_cast<f32x4*>(g.part_bias + (size_t)split * g.Mp + m0 + 4 * tid) = t;
+    }
+  }
+}
+
 static WgradOperands wgrad_operands(const WgradArgs& a) {
   return {a.b_mode == B_PLAIN, a.a_up2 != 0, a.W, a.P, a.Np, a.lda, a.ldb, a.bs_a, a.bs_b,
           (((uintptr_t)a.a | (uintptr_t)a.b) & 15) == 0};
@@ -1512,8 +1731,9 @@ static int run_wgrad(const WgradArgs& base, const WgradPlan& pl, WgradKernel k, 
     case WgradKernel::H3T: fn = up2 ? wgrad_h3t_kernel<true, 2> : wgrad_h3t_kernel<false, 2>; break;
     case WgradKernel::H3T_EXACT: fn = up2 ? wgrad_h3t_kernel<true, 2, false, true> : wgrad_h3t_kernel<false, 2, false, true>; break;
     case WgradKernel::H3T_TWIN: fn = wgrad_h3t_kernel<false, 2, true>; break;
+    case WgradKernel::H3T_TILE: fn = pl.bn == 256 ? wgrad_h3t_tile_kernel<true> : wgrad_h3t_tile_kernel<false>; break;
   }
-  if (k >= WgradKernel::H3T) name = up2 ? "wgrad_h3t<up2>" : "wgrad_h3t";
+  if (k >= WgradKernel::H3T) name = k == WgradKernel::H3T_TILE ? "wgrad_h3t_tile" : up2 ? "wgrad_h3t<up2>" : "wgrad_h3t";
   hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, a);
   return launch_status(name);
 }
@@ -1667,16 +1887,20 @@ static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* 
   a.split_stride = (int64_t)p.nxi * Cout * Cin;
   const double flop = 2.0 * p.nxi * (double)p.T * Cout * Cin;
   launch_hook("wino_wgrad_gemm", 0, s, flop);
-  rc = run_wgrad(a, p.gemm, choose_wgrad_kernel(p.gemm, wgrad_operands(a)), s, p.nxi);
+  // the 256 x 128 tile form (pis_tune key 58) lays its slabs out in the plan's regions: the same
+  // split_stride, no more splits than p.gemm's
+  const WgradKernel kern = choose_wgrad_kernel(p.gemm, wgrad_operands(a), &p.tile);
+  const WgradPlan& gp = kern == WgradKernel::H3T_TILE ? p.tile : p.gemm;
+  rc = run_wgrad(a, gp, kern, s, p.nxi);
   launch_hook("wino_wgrad_gemm", 1, s, flop);
   // up to 16 split slabs: the output transform sums them itself (no reduced copy of the 36 planes:
   // the separate slab reduction of a 14-slab 128 x 256 layer read 66 MB at 0.8 TB/s); many slabs
   // keep the parallel slab reduction
-  const WgradOutBias bf{gbias, gbias ? p.gemm.splits : 0, db, WINO4_BIAS_SCALE};
-  if (p.m == 4 && p.gemm.splits <= 16) {
-    if (!rc) rc = launch_wino_wgrad_out(part, Cout, Cin, dw, acc, s, p.m, p.gemm.splits, a.split_stride, bf);
+  const WgradOutBias bf{gbias, gbias ? gp.splits : 0, db, WINO4_BIAS_SCALE};
+  if (p.m == 4 && gp.splits <= 16) {
+    if (!rc) rc = launch_wino_wgrad_out(part, Cout, Cin, dw, acc, s, p.m, gp.splits, a.split_stride, bf);
   } else {
-    if (!rc) rc = reduce_slabs_pitched(part, p.gemm.splits, a.split_stride, a.split_stride, M, 0, s);
+    if (!rc) rc = reduce_slabs_pitched(part, gp.splits, a.split_stride, a.split_stride, M, 0, s);
     if (!rc) rc = launch_wino_wgrad_out(M, Cout, Cin, dw, acc, s, p.m, 1, 0, bf);
   }
   if (!rc && db && !gbias) rc = colsum(dz, ldz, (int64_t)B * H * W, Cout, db, acc, base + p.off_cs, p.total - p.off_cs, s);

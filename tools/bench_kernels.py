@@ -119,6 +119,23 @@ def main():
             return lib.pis_conv3x3_dgrad_ex(dz.data_ptr(), cout, w.data_ptr(), x.data_ptr(), cin, 0, dx.data_ptr(), cin,
                                             B, H, H, cin, cout, dflags | 16 | 32, wsx.data_ptr(), nwx, s)
         ops["pdgrad"] = pdgrad
+
+        # the Winograd weight gradient's GEMM and output transform alone: the forward's kept transform of x and
+        # the prepared transform of dz (written once, here), then pis_conv3x3_wgrad_keep with PIS_WINO_PREPARED
+        if "kwgrad" in opsel:
+            nk = lib.pis_conv3x3_keep_bytes(B, H, H, cin, cout)
+            keep = torch.empty(max(nk, 4) // 4, device=dev)
+            ok = nk > 0 and lib.pis_conv3x3_fwd_keep(x.data_ptr(), cin, w.data_ptr(), bias.data_ptr(), 0, y.data_ptr(),
+                                                     cout, B, H, H, cin, cout, 1, wsx.data_ptr(), nwx, keep.data_ptr(),
+                                                     s) == 0
+            ok = ok and lib.pis_conv3x3_bwd_prep(dz.data_ptr(), cout, B, H, H, cin, cout, wsx.data_ptr(), nwx,
+                                                 ws.data_ptr(), nws, s) == 1
+            if not ok:
+                print(f"{name:12s} kwgrad  (no kept / prepared Winograd weight gradient)", flush=True)
+                continue
+            ops["kwgrad"] = lambda: lib.pis_conv3x3_wgrad_keep(x.data_ptr(), cin, dz.data_ptr(), cout, dw.data_ptr(),
+                                                               db.data_ptr(), B, H, H, cin, cout, 16, ws.data_ptr(), nws,
+                                                               keep.data_ptr(), s)
         dbg = [int(d) for d in args.dbg.split(",") if d] or ([1] if args.noload else [])
         vlist = [(v, 0) for v in variants] + [(v, d) for d in dbg for v in variants]
         results = {}
@@ -133,8 +150,9 @@ def main():
         for op in opsel:
             line = f"{name:12s} {op:6s}"
             for v, nl in vlist:
-                ms = min(results[(op, v, nl)])
-                line += f"  v{v}{f'-d{nl}' if nl else ''}: {ms:7.3f} ms {flops / ms / 1e9:6.1f} TF/s"
+                ms = min(results[(op, v, nl)])  # min of the rounds, and their spread (max - min)
+                line += (f"  v{v}{f'-d{nl}' if nl else ''}: {ms:7.3f} ms (+{max(results[(op, v, nl)]) - ms:5.3f}) "
+                         f"{flops / ms / 1e9:6.1f} TF/s")
             print(line, flush=True)
         del x, dz, w, y, dx, ws, dw
         torch.cuda.empty_cache()

@@ -8,7 +8,7 @@ import csv
 import sys
 from collections import defaultdict
 
-DEFAULT = ["reduce_slabs", "reduce_rows_chunk", "conv3x3_wgrad_h3", "gemm_nt_h3_bk32", "wgrad_up2_tile", "wgrad_h3t", "wgrad_x6",
+DEFAULT = ["reduce_slabs", "reduce_rows_chunk", "conv3x3_wgrad_h3", "gemm_nt_h3_bk32", "wgrad_up2_tile", "wgrad_h3t_tile", "wgrad_h3t", "wgrad_x6",
            "conv3x3_h3_kernel", "convt_h3", "wino4_dz2", "wino4_dz_cols", "wino4_output_t", "wino4_output", "wino4_input", "wino4_wgrad_out",
            "wino4_gemm_out", "maxpool_bwd", "head_loss", "adamw"]
 
