@@ -952,6 +952,38 @@ int pis_pde_unroll_bwd(const float* u, const float* u0, const void* ckpt, const 
                        int B, int H, int W, float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
                        void* ws, size_t ws_bytes, pis_stream_t stream);
 
+/* ---- the layer above with its coefficients in device memory, and their gradient (no reference counterpart;
+ * pde.py:unroll_coef_vjp_np is the definition of record) ----
+ * coef points to five float32 in device memory, D, k, a, mu, dt in that order (4-byte aligned), read by every
+ * kernel at its start; 4 D, dt D and dt mu are formed on the device, each one rounded float32 product, as the
+ * host forms them for the entry points above. flags: PIS_EVOLVE_CLAMP | PIS_EVOLVE_MU; the host cannot see mu,
+ * so PIS_EVOLVE_MU says whether the mu (u0 - c) term is formed (with mu = 0 it adds a zero). With the same
+ * float32 values pis_pde_unroll_fwd_dev writes the bits of pis_pde_unroll_fwd, and pis_pde_unroll_bwd_dev
+ * the g_u and g_u0 of pis_pde_unroll_bwd.
+ * NO RANGE CHECK is made on the five values: it would be a host synchronisation. They are arithmetic operands
+ * only and enter no address, loop bound or guard of a memory access, so no value can make a kernel fault; a
+ * value outside the ranges pis_pde_evolve checks gives a map that means nothing. The caller keeps them in
+ * range (pde.py:LearnablePDELayer does so by construction).
+ * g_coef (may be NULL: no sums, the kernels of pis_pde_unroll_bwd): [B][5] float64, 8-byte aligned. Per image
+ * the sum over all pixels and steps of, with q, c, n as above and lap, r, t the forward step's from c,
+ *   q (dt lap)    q (dt r)    q (dt (k (0 - (c (1 - c)))))    q (dt (u0 - c)) [PIS_EVOLVE_MU, else 0]    q t
+ * each term float32, every operation rounded on its own, the sum float64: dL/dD, dL/dk, dL/da, dL/dmu, dL/ddt
+ * of that image's part of the loss. Order of the sum: a thread over its pixels and steps, the wave's xor
+ * butterfly, the 16 waves pairwise, a workgroup's launches in turn (the first stores into its slot of ws, the
+ * later ones add to it), then per image one wave over the tiles. No atomics: bitwise reproducible at a fixed
+ * Tb; across Tb the grouping differs, so the sums agree to H W steps 2^-53 times the sum of the terms'
+ * magnitudes. steps == 0: g_coef = 0. ws: pis_pde_unroll_bwd_dev_ws(B, H, W) bytes, the three maps of
+ * pis_pde_unroll_bwd_ws and one slot of 8 doubles per tile; it needs no clearing.
+ * PIS_ERR_ARG before any GPU work: the checks of the entry points above except the scalar ones; coef NULL or
+ * misaligned; g_coef misaligned; out, ckpt, g_u, g_u0, ws or g_coef overlapping coef or another argument. */
+#define PIS_EVOLVE_MU 2
+size_t pis_pde_unroll_bwd_dev_ws(int B, int H, int W);
+int pis_pde_unroll_fwd_dev(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B, int H,
+                           int W, const float* coef, int steps, int flags, int tb, pis_stream_t stream);
+int pis_pde_unroll_bwd_dev(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
+                           float* g_u0, double* g_coef, int B, int H, int W, const float* coef, int steps, int flags,
+                           int tb, void* ws, size_t ws_bytes, pis_stream_t stream);
+
 /* ---- exact squared Euclidean distance transform of a batch of binary images, and the per-pixel
  * surface distances between two boundary maps (no reference counterpart;
  * evaluate.py:distance_transform_sq_np / surface_distances) ----

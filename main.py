@@ -2,10 +2,12 @@
 the MI355X path. Build-only flags: --synthetic N_TRAIN N_VAL H W, --base-dir,
 --device-cache, --augment {flip,d4,affine}, --clip-grad-norm FLOAT,
 --skip-nonfinite, --ema-decay FLOAT, --no-ema-warmup, --pde-layer {rd,pf} with
---pde-layer-steps N and --pde-layer-{dt,mu,diffusion,threshold-a,epsilon}."""
+--pde-layer-steps N and --pde-layer-{dt,mu,diffusion,threshold-a,epsilon},
+--pde-layer-learn NAME [NAME ...] with --pde-layer-lr F."""
 import argparse
 
-from physics_informed_image_segmentation_amd.pde import add_refine_flags, refine_from_args
+from physics_informed_image_segmentation_amd.pde import (add_learn_flags, add_refine_flags, learn_from_args,
+                                                         refine_from_args)
 from physics_informed_image_segmentation_amd.train import train
 
 
@@ -44,8 +46,10 @@ def parse_args(argv=None):
     p.add_argument("--no-ema-warmup", action="store_true",
                    help="use --ema-decay from the first step instead of min(decay, (1 + k) / (10 + k))")
     add_refine_flags(p, prefix="pde-layer")
+    add_learn_flags(p)
     a = p.parse_args(argv)
     a.pde_layer_refine = refine_from_args(p, a, prefix="pde-layer")
+    a.pde_layer_learn, a.pde_layer_lr = learn_from_args(p, a, a.pde_layer_refine)
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
         p.error("--clip-grad-norm must be positive")
     if a.ema_decay is not None and not 0.0 < a.ema_decay < 1.0:
@@ -67,7 +71,9 @@ def main(argv=None):
                  device_data=not a.device_cache, device_cache=a.device_cache, augment=a.augment,
                  max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
                  ema_decay=a.ema_decay, ema_warmup=not a.no_ema_warmup,
-                 pde_layer=a.pde_layer_refine)
+                 pde_layer=a.pde_layer_refine,
+                 **({} if a.pde_layer_learn is None else {"pde_layer_learn": a.pde_layer_learn,
+                                                          "pde_layer_lr": a.pde_layer_lr}))
 
 
 if __name__ == "__main__":

@@ -25,7 +25,7 @@ from .loss import DiceBCELoss, DiceBCEPDELoss  # noqa: E402
 from .metrics import compute_dice_score, compute_dice_score_batch  # noqa: E402
 from .optim import AdamW  # noqa: E402
 from .pde import (PDELayer, PDERefine, PDERegularization, RefinedModel, create_pde_regularization, energies,  # noqa: E402
-                  energies_np, evolve, evolve_np, unroll, unroll_vjp_np)
+                  energies_np, evolve, evolve_np, unroll, unroll_vjp_np, LearnablePDELayer, unroll_coef_vjp_np)
 from .train import EarlyStopping, train, train_epoch, train_stage, validate  # noqa: E402
 from .unet import UNet, count_parameters  # noqa: E402
 from .evaluate_comparison import evaluate_and_compare, run_repeated_evaluations  # noqa: E402
@@ -47,5 +47,6 @@ __all__ = ["CellSegmentationDataset", "UNet", "DiceBCELoss", "DiceBCEPDELoss", "
            "Predictor", "clean_mask", "tile_plan", "gather_tiles_np", "blend_tiles_np",
            "PDERefine", "evolve", "evolve_np", "energies", "energies_np",
            "unroll", "unroll_vjp_np", "PDELayer", "RefinedModel",
+           "LearnablePDELayer", "unroll_coef_vjp_np",
            "distance_transform_sq", "distance_transform_sq_np", "surface_distances",
            "compute_hausdorff_percentile_batch", "compute_assd_batch", "compute_surface_dice_batch"]

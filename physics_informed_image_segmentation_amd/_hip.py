@@ -29,6 +29,7 @@ PIS_TUNE_UNROLL_TB = 57  # include/pis_capi.h: steps per checkpoint and per reve
 PIS_TUNE_WINO_WGRAD_TILE = 58  # include/pis_capi.h: Winograd weight-gradient GEMM on 256 x 128 tiles (0 never, 1 measured shapes, 2 / 3 forced)
 PIS_UNROLL_MAX_STEPS = 1024
 PIS_EVOLVE_CLAMP, PIS_EVOLVE_TILE_H, PIS_EVOLVE_TILE_W, PIS_EVOLVE_MAX_STEPS = 1, 32, 64, 65536
+PIS_EVOLVE_MU = 2  # include/pis_capi.h: pis_pde_unroll_*_dev form the mu (u0 - c) term
 PIS_CACHE_IMG_U8, PIS_CACHE_IMG_F32, PIS_CACHE_MASK_BITS, PIS_CACHE_MASK_F32 = 0, 1, 0, 1
 PIS_GRADNORM_SKIP_NONFINITE, PIS_GRADNORM_NSTATS = 1, 8
 LOSS_NTERMS = 8
@@ -135,6 +136,9 @@ _SIGNATURES = {
     "pis_pde_unroll_fwd": ([P, P, P, P, Z, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, I, P], c_int),
     "pis_pde_unroll_bwd": ([P, P, P, P, P, P, I, I, I, c_float, c_float, c_float, c_float, c_float, I, I, I, P, Z, P],
                            c_int),
+    "pis_pde_unroll_bwd_dev_ws": ([I, I, I], c_size_t),
+    "pis_pde_unroll_fwd_dev": ([P, P, P, P, Z, I, I, I, P, I, I, I, P], c_int),
+    "pis_pde_unroll_bwd_dev": ([P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, Z, P], c_int),
     "pis_pde_energies_ws": ([I, I, I], c_size_t),
     "pis_pde_energies": ([P, I, I, I, c_float, c_float, c_float, P, P, P, Z, P], c_int),
     "pis_edt_ws": ([I, I, I], c_size_t),

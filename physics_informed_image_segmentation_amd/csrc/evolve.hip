@@ -9,6 +9,16 @@
 //   pis_pde_unroll_fwd pis_pde_evolve's steps, keeping the state after every Tb-th step
 //   pis_pde_unroll_bwd the vector-Jacobian product of those steps, one launch per Tb steps, last first
 //                      (pde.py:unroll_vjp_np is its definition of record)
+//   pis_pde_unroll_fwd_dev / pis_pde_unroll_bwd_dev
+//                      the same two with D, k, a, mu, dt read from device memory, and on request the
+//                      gradient with respect to those five (pde.py:unroll_coef_vjp_np)
+//
+// Coefficients from device memory: a kernel reads coef[5] once at its start and forms 4 D, dt D and dt mu
+// with ev_mul, the three float32 products the host forms for the by-value entry points. The values are
+// arithmetic operands only: none enters an address, a loop bound or a branch that guards a memory access,
+// so no value (NaN and infinities included) can make a kernel read or write out of bounds. That path has
+// no range check, which would be a host synchronisation; pde.py:LearnablePDELayer keeps the values in
+// range by construction.
 //
 // Temporal blocking: a block owns an EV_TH x EV_TW output tile. It loads the tile plus a T-wide halo
 // through the reflect index (any number of periods: an image may be narrower than the halo), then
@@ -62,6 +72,7 @@ struct EvolveArgs {
   uint8_t* mask;     // the last launch only, may be NULL
   int H, W, nbx, nby, h;  // h <= T steps in this launch
   float D, k, a, mu, dt, thr;
+  const float* coef;  // not NULL: D, k, a, mu, dt are read from it (device memory), the five above unused
 };
 
 __device__ __forceinline__ float ev_lap(float c, float up, float dn, float lf, float rt) {
@@ -82,6 +93,10 @@ __global__ __launch_bounds__(EV_THREADS) void pde_evolve_kernel(EvolveArgs g) {
   const int H = g.H, W = g.W;
   const int64_t img = (int64_t)b * H * W;
   const float* __restrict__ src = g.src + img;
+  float cD = g.D, ck = g.k, ca = g.a, cmu = g.mu, cdt = g.dt;
+  if (g.coef) {  // uniform
+    cD = g.coef[0]; ck = g.coef[1]; ca = g.coef[2]; cmu = g.coef[3]; cdt = g.coef[4];
+  }
 
   for (int p = tid; p < PN; p += EV_THREADS) {
     const int ly = p / PW, lx = p - ly * PW;
@@ -99,10 +114,10 @@ __global__ __launch_bounds__(EV_THREADS) void pde_evolve_kernel(EvolveArgs g) {
     for (int p = s * PW + s + tid; p < end; p += EV_THREADS) {
       const float c = in[p];
       const float lap = ev_lap(c, in[p - PW], in[p + PW], in[p - 1], in[p + 1]);
-      float t = ev_mul(g.D, lap);
-      t = ev_add(t, ev_mul(g.k, ev_react(c, g.a)));
-      if (MU) t = ev_add(t, ev_mul(g.mu, ev_sub(plane0[p], c)));
-      float n = ev_add(c, ev_mul(g.dt, t));
+      float t = ev_mul(cD, lap);
+      t = ev_add(t, ev_mul(ck, ev_react(c, ca)));
+      if (MU) t = ev_add(t, ev_mul(cmu, ev_sub(plane0[p], c)));
+      float n = ev_add(c, ev_mul(cdt, t));
       if (CLAMP) {
         n = n < 0.f ? 0.f : n;
         n = n > 1.f ? 1.f : n;
@@ -171,6 +186,8 @@ struct UnrollBwdArgs {
   int first, fold;   // first: gz starts from 0; fold: gout = g + gz (u is its own u0, last launch)
   float k, a, mu, dt, fourD, dtD, dtmu;
   float D;
+  const float* coef;  // not NULL: D, k, a, mu, dt are read from it (device memory), the eight above unused
+  double* part;       // COEF: [blocks][UN_SLOT], a workgroup's sums of the five coefficient terms
 };
 
 __device__ __forceinline__ float un_clamp(float n) {
@@ -178,13 +195,24 @@ __device__ __forceinline__ float un_clamp(float n) {
   return n > 1.f ? 1.f : n;
 }
 
+constexpr int UN_NCOEF = 5, UN_SLOT = 8;  // D, k, a, mu, dt; a slot is padded to 8 doubles
+constexpr int UN_WAVES = UN_THREADS / 64;
+
 template <int T>
-constexpr size_t un_lds_bytes(bool mu) {
+constexpr size_t un_lds_bytes(bool mu, bool coef = false) {
   constexpr size_t PN = (size_t)(EV_TH + 4 * T) * (EV_TW + 4 * T);
-  return sizeof(float) * ((T + 3) * PN + (mu ? PN + (size_t)EV_TH * EV_TW : 0));
+  return sizeof(float) * ((T + 3) * PN + (mu ? PN + (size_t)EV_TH * EV_TW : 0)) +
+         (coef ? sizeof(double) * UN_WAVES * UN_NCOEF : 0);
 }
 
-template <bool MU, bool CLAMP, int T>
+// COEF (pde.py:unroll_coef_vjp_np is the definition): in the reverse step j the thread that
+// owns an in-image pixel of the tile also forms the five products of q with the step's derivative with
+// respect to D, k, a, mu and dt, from c_j and its four neighbours (the tile is 2 T rings inside the plane,
+// c_j is exact j <= T - 1 rings inside, so the neighbours are exact too), and adds them to five float64
+// sums it keeps over the launch's steps. Halo pixels add nothing: every pixel of the image is counted by the
+// one workgroup whose tile holds it. Then wave_sum_d, the 16 waves pairwise in a fixed order, and thread c
+// adds column c to the workgroup's own slot (the first launch of a backward stores instead).
+template <bool MU, bool CLAMP, int T, bool COEF>
 __global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArgs g) {
   constexpr int R = 2 * T, PH = EV_TH + 2 * R, PW = EV_TW + 2 * R, PN = PH * PW;
   extern __shared__ __attribute__((aligned(16))) float un_lds[];
@@ -192,11 +220,18 @@ __global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArg
   float* const gp = st + (T + 1) * PN;  // [2][PN]
   float* const z = gp + 2 * PN;         // MU: [PN] u0
   float* const gzt = z + PN;            // MU: [EV_TH * EV_TW]
+  double* const red = (double*)(st + (T + 3) * PN + (MU ? PN + EV_TH * EV_TW : 0));  // COEF: [UN_WAVES][UN_NCOEF]
   const int tid = threadIdx.x;
   const int bx = blockIdx.x % g.nbx, by = (blockIdx.x / g.nbx) % g.nby, b = blockIdx.x / (g.nbx * g.nby);
   const int y0 = by * EV_TH, x0 = bx * EV_TW;
   const int H = g.H, W = g.W, h = g.h;
   const int64_t img = (int64_t)b * H * W;
+  float cD = g.D, ck = g.k, ca = g.a, cmu = g.mu, cdt = g.dt, fourD = g.fourD, dtD = g.dtD, dtmu = g.dtmu;
+  if (g.coef) {  // uniform
+    cD = g.coef[0]; ck = g.coef[1]; ca = g.coef[2]; cmu = g.coef[3]; cdt = g.coef[4];
+    fourD = ev_mul(4.f, cD); dtD = ev_mul(cdt, cD); dtmu = ev_mul(cdt, cmu);
+  }
+  double acc[UN_NCOEF] = {0.0, 0.0, 0.0, 0.0, 0.0};
 
   for (int p = tid; p < PN; p += UN_THREADS) {
     const int ly = p / PW, lx = p - ly * PW;
@@ -227,10 +262,10 @@ __global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArg
       if (cl) {
         c = un_clamp(c); up = un_clamp(up); dn = un_clamp(dn); lf = un_clamp(lf); rt = un_clamp(rt);
       }
-      float t = ev_mul(g.D, ev_lap(c, up, dn, lf, rt));
-      t = ev_add(t, ev_mul(g.k, ev_react(c, g.a)));
-      if (MU) t = ev_add(t, ev_mul(g.mu, ev_sub(z[p], c)));
-      out[p] = ev_add(c, ev_mul(g.dt, t));
+      float t = ev_mul(cD, ev_lap(c, up, dn, lf, rt));
+      t = ev_add(t, ev_mul(ck, ev_react(c, ca)));
+      if (MU) t = ev_add(t, ev_mul(cmu, ev_sub(z[p], c)));
+      out[p] = ev_add(c, ev_mul(cdt, t));
     }
     __syncthreads();
   }
@@ -261,16 +296,37 @@ __global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArg
                               ev_add(ev_mul(wal, q_at(p - 1)), ev_mul(wbr, q_at(p + 1))));
       float c = cj[p];
       if (CLAMP && j > 0) c = un_clamp(c);
-      const float rp = ev_add(ev_mul(ev_sub(1.f, ev_mul(2.f, c)), ev_sub(c, g.a)), ev_mul(c, ev_sub(1.f, c)));
-      float s = ev_mul(g.k, rp);
-      s = ev_sub(s, g.fourD);
-      if (MU) s = ev_sub(s, g.mu);
-      const float d = ev_add(1.f, ev_mul(g.dt, s));
-      go[p] = ev_add(ev_mul(d, q), ev_mul(g.dtD, nb));
-      if (MU) {
+      const float rp = ev_add(ev_mul(ev_sub(1.f, ev_mul(2.f, c)), ev_sub(c, ca)), ev_mul(c, ev_sub(1.f, c)));
+      float s = ev_mul(ck, rp);
+      s = ev_sub(s, fourD);
+      if (MU) s = ev_sub(s, cmu);
+      const float d = ev_add(1.f, ev_mul(cdt, s));
+      go[p] = ev_add(ev_mul(d, q), ev_mul(dtD, nb));
+      if (MU || COEF) {
         const int ty = ly - R, tx = lx - R;
-        if ((unsigned)ty < (unsigned)EV_TH && (unsigned)tx < (unsigned)EV_TW)
-          gzt[ty * EV_TW + tx] = ev_add(gzt[ty * EV_TW + tx], ev_mul(g.dtmu, q));
+        if ((unsigned)ty < (unsigned)EV_TH && (unsigned)tx < (unsigned)EV_TW) {
+          if (MU) gzt[ty * EV_TW + tx] = ev_add(gzt[ty * EV_TW + tx], ev_mul(dtmu, q));
+          if (COEF) {  // the forward step from c_j again, as the recompute loop forms it
+            float up = cj[p - PW], dn = cj[p + PW], lf = cj[p - 1], rt = cj[p + 1];
+            if (CLAMP && j > 0) {
+              up = un_clamp(up); dn = un_clamp(dn); lf = un_clamp(lf); rt = un_clamp(rt);
+            }
+            const float lap = ev_lap(c, up, dn, lf, rt);
+            const float cc = ev_mul(c, ev_sub(1.f, c));
+            const float r = ev_mul(cc, ev_sub(c, ca));
+            float t = ev_mul(cD, lap);
+            t = ev_add(t, ev_mul(ck, r));
+            if (MU) {
+              const float zc = ev_sub(z[p], c);
+              t = ev_add(t, ev_mul(cmu, zc));
+              acc[3] += (double)ev_mul(q, ev_mul(cdt, zc));
+            }
+            acc[0] += (double)ev_mul(q, ev_mul(cdt, lap));
+            acc[1] += (double)ev_mul(q, ev_mul(cdt, r));
+            acc[2] += (double)ev_mul(q, ev_mul(cdt, ev_mul(ck, ev_sub(0.f, cc))));
+            acc[4] += (double)ev_mul(q, t);
+          }
+        }
       }
     }
     __syncthreads();
@@ -291,6 +347,45 @@ __global__ __launch_bounds__(UN_THREADS) void pde_unroll_bwd_kernel(UnrollBwdArg
     }
     if (g.fold) v = ev_add(v, zsum);
     g.gout[at] = v;
+  }
+
+  if (COEF) {
+#pragma unroll
+    for (int c = 0; c < UN_NCOEF; ++c) acc[c] = wave_sum_d(acc[c]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int c = 0; c < UN_NCOEF; ++c) red[(tid >> 6) * UN_NCOEF + c] = acc[c];
+    }
+    __syncthreads();
+    if (tid < UN_NCOEF) {  // ((w0 + w1) + (w2 + w3)) + ..., a balanced tree over the 16 waves
+      double w[UN_WAVES];
+#pragma unroll
+      for (int i = 0; i < UN_WAVES; ++i) w[i] = red[i * UN_NCOEF + tid];
+#pragma unroll
+      for (int n = UN_WAVES / 2; n >= 1; n >>= 1) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) w[i] = w[2 * i] + w[2 * i + 1];
+      }
+      double* const slot = g.part + (int64_t)UN_SLOT * blockIdx.x + tid;  // this workgroup's alone
+      *slot = g.first ? w[0] : *slot + w[0];
+    }
+  }
+}
+
+// one wave per image: lane l adds the slots of tiles l, l + 64, ... in ascending order, then the xor butterfly
+__global__ __launch_bounds__(64) void pde_coef_reduce_kernel(const double* __restrict__ part, int nt,
+                                                             double* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double s[UN_NCOEF] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = lane; i < nt; i += 64) {
+#pragma unroll
+    for (int c = 0; c < UN_NCOEF; ++c) s[c] += part[UN_SLOT * ((int64_t)b * nt + i) + c];
+  }
+#pragma unroll
+  for (int c = 0; c < UN_NCOEF; ++c) s[c] = wave_sum_d(s[c]);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < UN_NCOEF; ++c) out[UN_NCOEF * b + c] = s[c];
   }
 }
 
@@ -505,13 +600,30 @@ extern "C" size_t pis_pde_unroll_bwd_ws(int B, int H, int W) {
   return 3 * ev_map_bytes(B, H, W);  // two gradient maps in turn, and the running sum when g_u0 is NULL
 }
 
-// the scalar checks of pis_pde_evolve
-static int un_check_scalars(const char* who, int B, int H, int W, float D, float k, float a, float mu, float dt, int steps,
-                            int flags) {
+static size_t un_slot_bytes(int B, int H, int W) {
+  return (size_t)B * cdiv(H, EV_TH) * cdiv(W, EV_TW) * UN_SLOT * sizeof(double);
+}
+
+extern "C" size_t pis_pde_unroll_bwd_dev_ws(int B, int H, int W) {
+  if (!ev_shape_ok(B, H, W)) {
+    set_error("pis_pde_unroll_bwd_dev_ws: B >= 1 and 2 <= H, W <= 4096 are needed");
+    return 0;
+  }
+  return 3 * ev_map_bytes(B, H, W) + un_slot_bytes(B, H, W);  // pis_pde_unroll_bwd_ws's maps, then the slot table
+}
+
+static int un_check_shape(const char* who, int B, int H, int W, int steps, int flags, int known) {
   PIS_CHECK_ARG(ev_shape_ok(B, H, W), "%s: B = %d, H = %d, W = %d: B >= 1 and 2 <= H, W <= 4096 are needed", who, B, H, W);
   PIS_CHECK_ARG(steps >= 0 && steps <= PIS_UNROLL_MAX_STEPS, "%s: steps = %d: [0, %d] is needed", who, steps,
                 PIS_UNROLL_MAX_STEPS);
-  PIS_CHECK_ARG((flags & ~PIS_EVOLVE_CLAMP) == 0, "%s: unknown flags 0x%x", who, flags);
+  PIS_CHECK_ARG((flags & ~known) == 0, "%s: unknown flags 0x%x", who, flags);
+  return PIS_OK;
+}
+
+// the scalar checks of pis_pde_evolve
+static int un_check_scalars(const char* who, int B, int H, int W, float D, float k, float a, float mu, float dt, int steps,
+                            int flags) {
+  if (int rc = un_check_shape(who, B, H, W, steps, flags, PIS_EVOLVE_CLAMP)) return rc;
   PIS_CHECK_ARG(D >= 0.f && k >= 0.f && mu >= 0.f && a > 0.f && a < 1.f && dt > 0.f,
                 "%s: D >= 0, k >= 0, mu >= 0, 0 < a < 1 and dt > 0 are needed", who);
   PIS_CHECK_ARG((double)dt * (4.0 * D + (double)k + (double)mu) <= 1.0,
@@ -520,34 +632,34 @@ static int un_check_scalars(const char* who, int B, int H, int W, float D, float
   return PIS_OK;
 }
 
-extern "C" int pis_pde_unroll_fwd(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B, int H,
-                                  int W, float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
-                                  pis_stream_t stream) {
-  PIS_CHECK_ARG(u && out, "pis_pde_unroll_fwd: u or out is NULL");
-  if (int rc = un_check_scalars("pis_pde_unroll_fwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+// the checkpointed forward of both entry points: g holds the coefficients, by value or as g.coef
+static int un_fwd(const char* who, const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B,
+                  int H, int W, EvolveArgs g, bool with_mu, int steps, int flags, int tb, pis_stream_t stream) {
   const int T = un_tb(tb);
-  PIS_CHECK_ARG(T != 0, "pis_pde_unroll_fwd: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", tb,
+  PIS_CHECK_ARG(T != 0, "%s: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", who, tb,
                 PIS_TUNE_UNROLL_TB, tune_get(PIS_TUNE_UNROLL_TB));
-  PIS_CHECK_ARG(((uintptr_t)u | (uintptr_t)u0 | (uintptr_t)out | (uintptr_t)ckpt) % 16 == 0,
-                "pis_pde_unroll_fwd: u, u0, out and ckpt must be 16-byte aligned");
+  PIS_CHECK_ARG(((uintptr_t)u | (uintptr_t)u0 | (uintptr_t)out | (uintptr_t)ckpt) % 16 == 0 && (uintptr_t)g.coef % 4 == 0,
+                "%s: u, u0, out and ckpt must be 16-byte aligned (coef 4-byte)", who);
   const size_t bytes = (size_t)B * H * W * sizeof(float), map = ev_map_bytes(B, H, W);
   const int launches = steps == 0 ? 1 : (int)cdiv(steps, T);
   const size_t need = (size_t)(launches - 1) * map;
-  PIS_CHECK_ARG(need == 0 || (ckpt && ckpt_bytes >= need),
-                "pis_pde_unroll_fwd: checkpoint stack missing or too small (%zu < %zu bytes)", ckpt_bytes, need);
+  PIS_CHECK_ARG(need == 0 || (ckpt && ckpt_bytes >= need), "%s: checkpoint stack missing or too small (%zu < %zu bytes)",
+                who, ckpt_bytes, need);
   PIS_CHECK_ARG(!ev_overlap(out, bytes, u, bytes) && !(u0 && ev_overlap(out, bytes, u0, bytes)) &&
                     (!need || (!ev_overlap(ckpt, need, u, bytes) && !ev_overlap(ckpt, need, out, bytes) &&
                                !(u0 && ev_overlap(ckpt, need, u0, bytes)))),
-                "pis_pde_unroll_fwd: out or ckpt overlaps another map");
-  EvolveArgs g{};
+                "%s: out or ckpt overlaps another map", who);
+  const size_t cb = UN_NCOEF * sizeof(float);
+  PIS_CHECK_ARG(!g.coef || (!ev_overlap(out, bytes, g.coef, cb) && !(need && ev_overlap(ckpt, need, g.coef, cb))),
+                "%s: out or ckpt overlaps coef", who);
   g.H = H; g.W = W;
   g.nbx = (int)cdiv(W, EV_TW);
   g.nby = (int)cdiv(H, EV_TH);
-  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt; g.thr = 0.f;
+  g.thr = 0.f;
   g.u0 = u0 ? u0 : u;
   g.mask = nullptr;
   const unsigned blocks = (unsigned)((int64_t)B * g.nbx * g.nby);
-  const bool with_mu = mu != 0.f, clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
+  const bool clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
   const float* src = u;
   for (int i = 0, left = steps; i < launches; ++i) {
     g.src = src;
@@ -567,82 +679,112 @@ extern "C" int pis_pde_unroll_fwd(const float* u, const float* u0, float* out, v
   return PIS_OK;
 }
 
-template <bool MU, bool CLAMP>
+extern "C" int pis_pde_unroll_fwd(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B, int H,
+                                  int W, float D, float k, float a, float mu, float dt, int steps, int flags, int tb,
+                                  pis_stream_t stream) {
+  PIS_CHECK_ARG(u && out, "pis_pde_unroll_fwd: u or out is NULL");
+  if (int rc = un_check_scalars("pis_pde_unroll_fwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+  EvolveArgs g{};
+  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt;
+  return un_fwd("pis_pde_unroll_fwd", u, u0, out, ckpt, ckpt_bytes, B, H, W, g, mu != 0.f, steps, flags, tb, stream);
+}
+
+extern "C" int pis_pde_unroll_fwd_dev(const float* u, const float* u0, float* out, void* ckpt, size_t ckpt_bytes, int B,
+                                      int H, int W, const float* coef, int steps, int flags, int tb,
+                                      pis_stream_t stream) {
+  PIS_CHECK_ARG(u && out && coef, "pis_pde_unroll_fwd_dev: u, out or coef is NULL");
+  if (int rc = un_check_shape("pis_pde_unroll_fwd_dev", B, H, W, steps, flags, PIS_EVOLVE_CLAMP | PIS_EVOLVE_MU)) return rc;
+  EvolveArgs g{};
+  g.coef = coef;
+  return un_fwd("pis_pde_unroll_fwd_dev", u, u0, out, ckpt, ckpt_bytes, B, H, W, g, (flags & PIS_EVOLVE_MU) != 0, steps,
+                flags, tb, stream);
+}
+
+template <bool MU, bool CLAMP, bool COEF>
 static void un_launch(int T, unsigned blocks, hipStream_t s, const UnrollBwdArgs& a) {
   switch (T) {
     case 1:
-      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 1>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<1>(MU), s, a);
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 1, COEF>), dim3(blocks), dim3(UN_THREADS),
+                         un_lds_bytes<1>(MU, COEF), s, a);
       break;
     case 2:
-      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 2>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<2>(MU), s, a);
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 2, COEF>), dim3(blocks), dim3(UN_THREADS),
+                         un_lds_bytes<2>(MU, COEF), s, a);
       break;
     default:
-      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 4>), dim3(blocks), dim3(UN_THREADS), un_lds_bytes<4>(MU), s, a);
+      hipLaunchKernelGGL((pde_unroll_bwd_kernel<MU, CLAMP, 4, COEF>), dim3(blocks), dim3(UN_THREADS),
+                         un_lds_bytes<4>(MU, COEF), s, a);
       break;
   }
 }
-static_assert(un_lds_bytes<4>(true) <= 160 * 1024, "the reverse sweep's planes must fit one workgroup's LDS");
+template <bool COEF>
+static void un_launch_flags(bool with_mu, bool clamp, int T, unsigned blocks, hipStream_t s, const UnrollBwdArgs& a) {
+  if (with_mu) {
+    if (clamp) un_launch<true, true, COEF>(T, blocks, s, a);
+    else un_launch<true, false, COEF>(T, blocks, s, a);
+  } else {
+    if (clamp) un_launch<false, true, COEF>(T, blocks, s, a);
+    else un_launch<false, false, COEF>(T, blocks, s, a);
+  }
+}
+static_assert(un_lds_bytes<4>(true, true) <= 160 * 1024, "the reverse sweep's planes must fit one workgroup's LDS");
 
-extern "C" int pis_pde_unroll_bwd(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
-                                  float* g_u0, int B, int H, int W, float D, float k, float a, float mu, float dt,
-                                  int steps, int flags, int tb, void* ws, size_t ws_bytes, pis_stream_t stream) {
-  PIS_CHECK_ARG(u && g_out && g_u, "pis_pde_unroll_bwd: u, g_out or g_u is NULL");
-  PIS_CHECK_ARG(u0 || !g_u0, "pis_pde_unroll_bwd: g_u0 without u0 (u is then its own u0 and g_u holds the sum)");
-  if (int rc = un_check_scalars("pis_pde_unroll_bwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+// the reverse sweep of both entry points: g holds the coefficients, by value or as g.coef. g_coef (with
+// g.coef only): the COEF kernels, their slot table behind the three maps of ws, and the reduce kernel.
+static int un_bwd(const char* who, const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
+                  float* g_u0, double* g_coef, int B, int H, int W, UnrollBwdArgs g, bool with_mu, int steps, int flags,
+                  int tb, void* ws, size_t ws_bytes, pis_stream_t stream) {
   const int T = un_tb(tb);
-  PIS_CHECK_ARG(T != 0, "pis_pde_unroll_bwd: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", tb,
+  PIS_CHECK_ARG(T != 0, "%s: temporal block %d (pis_tune key %d holds %d): 1, 2 or 4 is needed", who, tb,
                 PIS_TUNE_UNROLL_TB, tune_get(PIS_TUNE_UNROLL_TB));
   PIS_CHECK_ARG(((uintptr_t)u | (uintptr_t)u0 | (uintptr_t)ckpt | (uintptr_t)g_out | (uintptr_t)g_u | (uintptr_t)g_u0 |
-                 (uintptr_t)ws) % 16 == 0,
-                "pis_pde_unroll_bwd: every map, ckpt and ws must be 16-byte aligned");
+                 (uintptr_t)ws) % 16 == 0 && (uintptr_t)g.coef % 4 == 0 && (uintptr_t)g_coef % 8 == 0,
+                "%s: every map, ckpt and ws must be 16-byte aligned (coef 4-byte, g_coef 8-byte)", who);
   const size_t bytes = (size_t)B * H * W * sizeof(float), map = ev_map_bytes(B, H, W);
   const int launches = steps == 0 ? 0 : (int)cdiv(steps, T);
   const size_t stack = launches > 1 ? (size_t)(launches - 1) * map : 0;
-  PIS_CHECK_ARG(stack == 0 || ckpt, "pis_pde_unroll_bwd: ckpt is NULL (%d checkpoints are needed)", launches - 1);
-  const bool with_mu = mu != 0.f, clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
+  PIS_CHECK_ARG(stack == 0 || ckpt, "%s: ckpt is NULL (%d checkpoints are needed)", who, launches - 1);
+  const bool clamp = (flags & PIS_EVOLVE_CLAMP) != 0;
   const bool carry_in_ws = with_mu && !g_u0;
   const size_t need = steps == 0 ? 0 : (size_t)(std::min(launches - 1, 2)) * map;  // the gradient maps in turn
-  const size_t need_all = carry_in_ws ? 3 * map : need;                           // the running sum sits third
-  PIS_CHECK_ARG(need_all == 0 || (ws && ws_bytes >= need_all),
-                "pis_pde_unroll_bwd: workspace missing or too small (%zu < %zu bytes)", ws_bytes, need_all);
+  const size_t slots = g_coef && steps ? un_slot_bytes(B, H, W) : 0;                // behind the three maps
+  const size_t need_all = slots ? 3 * map + slots : (carry_in_ws ? 3 * map : need);  // the running sum sits third
+  PIS_CHECK_ARG(need_all == 0 || (ws && ws_bytes >= need_all), "%s: workspace missing or too small (%zu < %zu bytes)", who,
+                ws_bytes, need_all);
+  const size_t cb = UN_NCOEF * sizeof(float), gcb = (size_t)B * UN_NCOEF * sizeof(double);
   {
-    const void* p[7] = {g_u, g_u0, need_all ? ws : nullptr, g_out, u, u0, stack ? ckpt : nullptr};
-    const size_t n[7] = {bytes, bytes, need_all, bytes, bytes, bytes, stack};
-    // what is written (the first three) meets nothing; the inputs may meet each other (u0 may be u)
+    const void* p[9] = {g_u, g_u0, need_all ? ws : nullptr, g_coef, g_out, u, u0, stack ? ckpt : nullptr, g.coef};
+    const size_t n[9] = {bytes, bytes, need_all, gcb, bytes, bytes, bytes, stack, cb};
+    // what is written (the first four) meets nothing; the inputs may meet each other (u0 may be u)
     bool ok = true;
-    for (int i = 0; i < 3; ++i)
-      for (int j = i + 1; j < 7; ++j)
+    for (int i = 0; i < 4; ++i)
+      for (int j = i + 1; j < 9; ++j)
         ok = ok && !(p[i] && p[j] && n[i] && n[j] && ev_overlap(p[i], n[i], p[j], n[j]));
-    PIS_CHECK_ARG(ok, "pis_pde_unroll_bwd: g_u, g_u0 or ws overlaps another map");
+    PIS_CHECK_ARG(ok, "%s: g_u, g_u0, ws or g_coef overlaps another argument", who);
   }
   hipStream_t s = (hipStream_t)stream;
   if ((steps == 0 || !with_mu) && g_u0) {  // nothing reaches u0
     const hipError_t e = hipMemsetAsync(g_u0, 0, bytes, s);
     if (e != hipSuccess) {
-      set_error("pis_pde_unroll_bwd: clearing g_u0: %s", hipGetErrorString(e));
+      set_error("%s: clearing g_u0: %s", who, hipGetErrorString(e));
       return PIS_ERR_LAUNCH;
     }
   }
   if (steps == 0) {  // the identity
-    const hipError_t e = hipMemcpyAsync(g_u, g_out, bytes, hipMemcpyDeviceToDevice, s);
+    hipError_t e = hipMemcpyAsync(g_u, g_out, bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && g_coef) e = hipMemsetAsync(g_coef, 0, gcb, s);
     if (e != hipSuccess) {
-      set_error("pis_pde_unroll_bwd: copying g_out: %s", hipGetErrorString(e));
+      set_error("%s: copying g_out: %s", who, hipGetErrorString(e));
       return PIS_ERR_LAUNCH;
     }
     return PIS_OK;
   }
-  UnrollBwdArgs g{};
   g.H = H; g.W = W;
   g.nbx = (int)cdiv(W, EV_TW);
   g.nby = (int)cdiv(H, EV_TH);
-  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt;
-  {
-    // float32 products formed once, each rounded on its own (volatile: no contraction, no folding in double)
-    volatile float four_d = 4.f * D, dt_d = dt * D, dt_mu = dt * mu;
-    g.fourD = four_d; g.dtD = dt_d; g.dtmu = dt_mu;
-  }
   g.u0 = u0 ? u0 : u;
   g.gz = with_mu ? (g_u0 ? g_u0 : (float*)((char*)ws + 2 * map)) : nullptr;
+  g.part = g_coef ? (double*)((char*)ws + 3 * map) : nullptr;
   const unsigned blocks = (unsigned)((int64_t)B * g.nbx * g.nby);
   float* scratch[2] = {(float*)ws, (float*)((char*)ws + map)};
   const float* gin = g_out;
@@ -655,17 +797,46 @@ extern "C" int pis_pde_unroll_bwd(const float* u, const float* u0, const void* c
     g.gout = last ? g_u : scratch[t & 1];  // launch t reads scratch[(t - 1) & 1] (g_out for t == 0)
     g.first = t == 0;
     g.fold = last && !u0;
-    if (with_mu) {
-      if (clamp) un_launch<true, true>(T, blocks, s, g);
-      else un_launch<true, false>(T, blocks, s, g);
-    } else {
-      if (clamp) un_launch<false, true>(T, blocks, s, g);
-      else un_launch<false, false>(T, blocks, s, g);
-    }
+    if (g_coef) un_launch_flags<true>(with_mu, clamp, T, blocks, s, g);
+    else un_launch_flags<false>(with_mu, clamp, T, blocks, s, g);
     if (int rc = launch_status("pde_unroll_bwd")) return rc;
     gin = g.gout;
   }
+  if (g_coef) {
+    hipLaunchKernelGGL(pde_coef_reduce_kernel, dim3((unsigned)B), dim3(64), 0, s, (const double*)g.part, g.nbx * g.nby,
+                       g_coef);
+    return launch_status("pde_coef_reduce");
+  }
   return PIS_OK;
+}
+
+extern "C" int pis_pde_unroll_bwd(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
+                                  float* g_u0, int B, int H, int W, float D, float k, float a, float mu, float dt,
+                                  int steps, int flags, int tb, void* ws, size_t ws_bytes, pis_stream_t stream) {
+  PIS_CHECK_ARG(u && g_out && g_u, "pis_pde_unroll_bwd: u, g_out or g_u is NULL");
+  PIS_CHECK_ARG(u0 || !g_u0, "pis_pde_unroll_bwd: g_u0 without u0 (u is then its own u0 and g_u holds the sum)");
+  if (int rc = un_check_scalars("pis_pde_unroll_bwd", B, H, W, D, k, a, mu, dt, steps, flags)) return rc;
+  UnrollBwdArgs g{};
+  g.D = D; g.k = k; g.a = a; g.mu = mu; g.dt = dt;
+  {
+    // float32 products formed once, each rounded on its own (volatile: no contraction, no folding in double)
+    volatile float four_d = 4.f * D, dt_d = dt * D, dt_mu = dt * mu;
+    g.fourD = four_d; g.dtD = dt_d; g.dtmu = dt_mu;
+  }
+  return un_bwd("pis_pde_unroll_bwd", u, u0, ckpt, g_out, g_u, g_u0, nullptr, B, H, W, g, mu != 0.f, steps, flags, tb, ws,
+                ws_bytes, stream);
+}
+
+extern "C" int pis_pde_unroll_bwd_dev(const float* u, const float* u0, const void* ckpt, const float* g_out, float* g_u,
+                                      float* g_u0, double* g_coef, int B, int H, int W, const float* coef, int steps,
+                                      int flags, int tb, void* ws, size_t ws_bytes, pis_stream_t stream) {
+  PIS_CHECK_ARG(u && g_out && g_u && coef, "pis_pde_unroll_bwd_dev: u, g_out, g_u or coef is NULL");
+  PIS_CHECK_ARG(u0 || !g_u0, "pis_pde_unroll_bwd_dev: g_u0 without u0 (u is then its own u0 and g_u holds the sum)");
+  if (int rc = un_check_shape("pis_pde_unroll_bwd_dev", B, H, W, steps, flags, PIS_EVOLVE_CLAMP | PIS_EVOLVE_MU)) return rc;
+  UnrollBwdArgs g{};
+  g.coef = coef;
+  return un_bwd("pis_pde_unroll_bwd_dev", u, u0, ckpt, g_out, g_u, g_u0, g_coef, B, H, W, g, (flags & PIS_EVOLVE_MU) != 0,
+                steps, flags, tb, ws, ws_bytes, stream);
 }
 
 static bool en_shape_ok(int B, int H, int W) {

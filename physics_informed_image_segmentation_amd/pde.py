@@ -45,6 +45,9 @@ _f32 = np.float32
 # the legal temporal blocks Tb of pis_pde_unroll_fwd / _bwd and the bound on their step count
 UNROLL_TB_VALUES = (1, 2, 4)
 UNROLL_MAX_STEPS = _hip.PIS_UNROLL_MAX_STEPS
+# the order of the coefficients wherever five of them travel together: the device tensor of
+# ``unroll(coef=...)``, the columns of ``unroll_coef_vjp_np`` and of pis_pde_unroll_bwd_dev's g_coef
+COEF_NAMES = ("D", "k", "a", "mu", "dt")
 
 
 def evolve_temporal_block(value: Optional[int] = None) -> int:
@@ -252,6 +255,86 @@ def unroll_vjp_np(u, g_out, steps: int, D, k, a, mu=0.0, dt=None, clamp: bool = 
     return g.reshape(shape), gz.reshape(shape)
 
 
+def unroll_coef_vjp_np(u, g_out, steps: int, D, k, a, mu=0.0, dt=None, clamp: bool = True, u0=None,
+                       with_mu: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The definition of ``unroll``'s gradient with respect to the coefficients: per image
+    the derivative of ``sum(g_out * evolve_np(u, ...))`` with respect to D, k, a, mu and dt (columns in
+    the order of ``COEF_NAMES``), the five taken as independent. Returns ``(sums, abs_sums)``, both
+    (B, 5) float64. With ``c`` a step's input, ``lap``, ``r``, ``t`` as ``evolve_np`` forms them from
+    it and ``q`` the masked incoming gradient of ``unroll_vjp_np``, the step adds per pixel, in float32
+    with every operation rounded on its own::
+
+        eD  = q * (dt * lap)
+        ek  = q * (dt * r)                           r = (c (1 - c)) (c - a)
+        ea  = q * (dt * (k * (0 - (c (1 - c)))))
+        emu = q * (dt * (z - c))                     with the mu term only, else 0
+        edt = q * t
+
+    ``sums`` is the float64 sum of those float32 terms over all pixels and steps, ``abs_sums`` the
+    float64 sum of their magnitudes: the order of the sum is not part of the definition, and two
+    correct sums differ by at most ``H W steps 2^-53 abs_sums``. ``with_mu=None``: the mu term is
+    present when ``mu != 0``, as in ``evolve_np``; ``with_mu=True`` keeps ``t = t + mu (z - c)`` and
+    ``s = s - mu`` for ``mu == 0`` too (they add zeros), which is what the device path does when mu is
+    learnable: the mu column is then the derivative at ``mu = 0``. Arguments are checked as
+    ``unroll_vjp_np`` checks them; ``steps == 0`` gives zeros."""
+    steps, D, k, a, mu, dt = _check_unroll(steps, D, k, a, mu, dt)
+    c = _maps_np(u, "unroll_coef_vjp_np").copy()
+    g = _maps_np(g_out, "unroll_coef_vjp_np: g_out")
+    if g.shape != c.shape:
+        raise ValueError(f"unroll_coef_vjp_np: g_out {g.shape} does not match u {c.shape}")
+    g = g.copy()
+    z = c if u0 is None else _maps_np(u0, "unroll_coef_vjp_np: u0")
+    if z.shape != c.shape:
+        raise ValueError(f"unroll_coef_vjp_np: u0 {z.shape} does not match u {c.shape}")
+    z = z.copy()
+    with_mu = bool(mu != 0) if with_mu is None else bool(with_mu)
+    one, two, four, zero = _f32(1), _f32(2), _f32(4), _f32(0)
+    four_d, dt_d = four * D, dt * D
+    (wa_h, wb_h), (wa_w, wb_w) = _adjoint_weights_np(c.shape[1]), _adjoint_weights_np(c.shape[2])
+    wa_h, wb_h = wa_h[None, :, None], wb_h[None, :, None]
+    wa_w, wb_w = wa_w[None, None, :], wb_w[None, None, :]
+    steps_kept = []
+    sums, abs_sums = np.zeros((c.shape[0], 5)), np.zeros((c.shape[0], 5))
+    with np.errstate(all="ignore"):
+        for _ in range(steps):
+            up, dn, lf, rt = _neighbours_np(c)
+            lap = ((up + dn) + (lf + rt)) - four * c
+            cc = c * (one - c)
+            r = cc * (c - a)
+            t = D * lap
+            t = t + k * r
+            if with_mu:
+                t = t + mu * (z - c)
+            n = c + dt * t
+            steps_kept.append((c, lap, cc, r, t, ~(n < zero) & ~(n > one) if clamp else None))
+            if clamp:
+                n = np.where(n < zero, zero, n)
+                n = np.where(n > one, one, n)
+            c = n.astype(np.float32, copy=False)
+        for c, lap, cc, r, t, ok in reversed(steps_kept):
+            q = g if ok is None else np.where(ok, g, zero)
+            terms = [q * (dt * lap), q * (dt * r), q * (dt * (k * (zero - cc))),
+                     q * (dt * (z - c)) if with_mu else np.zeros_like(q), q * t]
+            for i, e in enumerate(terms):
+                assert e.dtype == np.float32
+                e = e.astype(np.float64)
+                sums[:, i] += e.sum(axis=(1, 2))
+                abs_sums[:, i] += np.abs(e).sum(axis=(1, 2))
+            p = np.pad(q, ((0, 0), (1, 1), (1, 1)))
+            fu, fd = wa_h * p[:, :-2, 1:-1], wb_h * p[:, 2:, 1:-1]
+            fl, fr = wa_w * p[:, 1:-1, :-2], wb_w * p[:, 1:-1, 2:]
+            nb = (fu + fd) + (fl + fr)
+            rp = ((one - two * c) * (c - a)) + (c * (one - c))
+            s = k * rp
+            s = s - four_d
+            if with_mu:
+                s = s - mu
+            d = one + dt * s
+            g = d * q + dt_d * nb
+            assert g.dtype == np.float32
+    return sums, abs_sums
+
+
 def energies_np(u, D, a, eps) -> Tuple[np.ndarray, np.ndarray]:
     """The definition of ``energies``: per image of float32 maps ``u``, ``(out (B, 2) float64,
     interface (B,) int64)`` with ``out[:, 0]`` the mean of ``double(res)^2``,
@@ -343,6 +426,24 @@ def add_refine_flags(ap, prefix: str = "refine"):
                     help=f"reaction threshold a of {f} rd, in (0, 1) (default: 0.5)")
     ap.add_argument(f"{f}-epsilon", type=float, default=0.05, metavar="F",
                     help=f"interface width of {f} pf (default: 0.05)")
+    if not layer:
+        ap.add_argument(f"{f}-file", default=None, metavar="PATH",
+                        help="a PDERefine written as JSON (steps, D, k, a, mu, dt, clamp), such as the "
+                             "output/pde_layer_<stamp>.json of a training run with learned coefficients, which the "
+                             f"presets of {f} may not be able to express; exclusive with {f}")
+
+
+def refine_from_file(path) -> "PDERefine":
+    """The PDERefine a JSON file holds (the keys of ``PDERefine.kwargs()``). Raises ValueError."""
+    import json
+    try:
+        with open(path) as fh:
+            kw = json.load(fh)
+        if not isinstance(kw, dict):
+            raise ValueError("a JSON object is needed")
+        return PDERefine(**kw)
+    except (OSError, TypeError, json.JSONDecodeError) as e:
+        raise ValueError(f"{path}: {e}") from e
 
 
 def refine_from_args(ap, args, prefix: str = "refine"):
@@ -351,6 +452,14 @@ def refine_from_args(ap, args, prefix: str = "refine"):
     f, dest = f"--{prefix}", prefix.replace("-", "_")
     get = lambda name: getattr(args, f"{dest}_{name}")  # noqa: E731
     kind, steps = getattr(args, dest), get("steps")
+    path = getattr(args, f"{dest}_file", None)
+    if path is not None:
+        if kind is not None or steps is not None:
+            ap.error(f"{f}-file holds the whole refinement: give it without {f} and {f}-steps")
+        try:
+            return refine_from_file(path)
+        except ValueError as e:
+            ap.error(f"{f}-file: {e}")
     if kind is None:
         if steps is not None:
             ap.error(f"{f}-steps needs {f} {{rd,pf}}")
@@ -365,6 +474,36 @@ def refine_from_args(ap, args, prefix: str = "refine"):
         return PDERefine.phase_field(steps, get("epsilon"), mu=get("mu"), dt=get("dt"))
     except ValueError as e:
         ap.error(f"{f}: {e}")
+
+
+def add_learn_flags(ap):
+    """--pde-layer-learn and --pde-layer-lr on a parser that has the --pde-layer set (main.py)."""
+    ap.add_argument("--pde-layer-learn", nargs="+", default=None, metavar="NAME", choices=list(LEARNABLE_NAMES),
+                    help="train these coefficients of --pde-layer with the weights, from the values the other "
+                         f"--pde-layer flags give: any of {', '.join(LEARNABLE_NAMES)} (eps ties D and k as "
+                         "--pde-layer pf does and excludes both; a coefficient that starts at 0 cannot be "
+                         "learned). dt follows as the same fraction of the stability bound (default: off)")
+    ap.add_argument("--pde-layer-lr", type=float, default=None, metavar="F",
+                    help="learning rate of the coefficients' Adam (default: the stage's learning rate)")
+
+
+def learn_from_args(ap, args, refine: Optional["PDERefine"]):
+    """``(learn, lr)`` of the parsed --pde-layer-learn / --pde-layer-lr, ``(None, None)`` when off; a bad
+    combination ends in ap.error."""
+    learn, lr = args.pde_layer_learn, args.pde_layer_lr
+    if learn is None:
+        if lr is not None:
+            ap.error("--pde-layer-lr needs --pde-layer-learn")
+        return None, None
+    if refine is None:
+        ap.error("--pde-layer-learn needs --pde-layer {rd,pf}")
+    if lr is not None and not lr > 0:
+        ap.error("--pde-layer-lr must be positive")
+    try:
+        LearnablePDELayer(refine, learn=tuple(learn))
+    except ValueError as e:
+        ap.error(f"--pde-layer-learn: {e}")
+    return tuple(learn), lr
 
 
 def refine_flags(refine: "PDERefine", kind: Optional[str] = None, prefix: str = "refine") -> str:
@@ -485,16 +624,98 @@ class _Unroll(torch.autograd.Function):
                 None, None, None, None, None, None, None)
 
 
+class _UnrollDev(torch.autograd.Function):
+    """``pis_pde_unroll_fwd_dev`` / ``pis_pde_unroll_bwd_dev``: ``_Unroll`` with the five coefficients
+    in a (5,) float32 CUDA tensor (``COEF_NAMES`` order) that the kernels read, and its gradient when
+    it requires one: the per-image table of the reverse sweep, summed over the batch in float64."""
+
+    @staticmethod
+    def forward(ctx, u, z, coef, steps, clamp, with_mu):
+        uc = _maps_cuda(u, "unroll")
+        zc = None if z is None else _maps_cuda(z, "unroll: u0")
+        cc = coef.detach().contiguous()
+        B, H, W = uc.shape[0], uc.shape[-2], uc.shape[-1]
+        flags = (_hip.PIS_EVOLVE_CLAMP if clamp else 0) | (_hip.PIS_EVOLVE_MU if with_mu else 0)
+        out = torch.empty_like(uc)
+        with torch.cuda.device(uc.device):
+            tb = int(_hip.lib().pis_tune(_hip.PIS_TUNE_UNROLL_TB, -1))  # read once: the backward runs with this one
+            nbytes = int(_hip.lib().pis_pde_unroll_ws(B, H, W, steps, tb))
+            ckpt = torch.empty(nbytes, dtype=torch.uint8, device=uc.device) if nbytes else None
+            _hip.call("pis_pde_unroll_fwd_dev", _hip.ptr(uc), _hip.ptr(zc), _hip.ptr(out), _hip.ptr(ckpt), nbytes, B, H,
+                      W, _hip.ptr(cc), steps, flags, tb, _hip.stream_handle(uc.device))
+        ctx.save_for_backward(uc, zc, ckpt, cc)
+        ctx.args = (B, H, W, steps, flags, tb)
+        ctx.shapes = (u.shape, None if z is None else z.shape)
+        return out.reshape(u.shape)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        uc, zc, ckpt, cc = ctx.saved_tensors
+        B, H, W, steps, flags, tb = ctx.args
+        if g_out.dtype != torch.float32:
+            raise TypeError(f"unroll: float32 gradient expected, got {g_out.dtype}")
+        g = g_out.contiguous()
+        g_u = torch.empty_like(uc)
+        g_z = torch.empty_like(uc) if zc is not None and ctx.needs_input_grad[1] else None
+        table = torch.empty((B, len(COEF_NAMES)), dtype=torch.float64, device=uc.device) if ctx.needs_input_grad[2] else None
+        with torch.cuda.device(uc.device):
+            nbytes = int(_hip.lib().pis_pde_unroll_bwd_dev_ws(B, H, W))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=uc.device)
+            _hip.call("pis_pde_unroll_bwd_dev", _hip.ptr(uc), _hip.ptr(zc), _hip.ptr(ckpt), _hip.ptr(g), _hip.ptr(g_u),
+                      _hip.ptr(g_z), _hip.ptr(table), B, H, W, _hip.ptr(cc), steps, flags, tb, _hip.ptr(ws), nbytes,
+                      _hip.stream_handle(uc.device))
+        return (g_u.reshape(ctx.shapes[0]), None if g_z is None else g_z.reshape(ctx.shapes[1]),
+                None if table is None else table.sum(0).to(torch.float32), None, None, None)
+
+
+def _unroll_dev(u, u0, coef, steps, clamp, with_mu, refine, scalars_given) -> torch.Tensor:
+    """``unroll(coef=...)``: the argument checks, then ``_UnrollDev``."""
+    if refine is not None or scalars_given:
+        raise ValueError("unroll: coef stands in place of a PDERefine and of D, k, a, mu and dt: give steps, clamp and "
+                         "with_mu beside it, nothing else")
+    if not isinstance(with_mu, bool):
+        raise ValueError("unroll: with coef, with_mu=True or False is needed: the host does not read mu")
+    if steps is None or isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= UNROLL_MAX_STEPS:
+        raise ValueError(f"unroll: steps = {steps!r}: an integer in [0, {UNROLL_MAX_STEPS}] is needed")
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or tuple(coef.shape) != (len(COEF_NAMES),):
+        raise ValueError(f"unroll: coef must be a float32 tensor of shape ({len(COEF_NAMES)},): {', '.join(COEF_NAMES)}")
+    _maps_cuda(u, "unroll")
+    if coef.device != u.device:
+        raise ValueError(f"unroll: coef on {coef.device}, u on {u.device}")
+    if u0 is not None:
+        _maps_cuda(u0, "unroll: u0")
+        if u0.shape[0] != u.shape[0] or tuple(u0.shape[-2:]) != tuple(u.shape[-2:]) or u0.device != u.device:
+            raise ValueError(f"unroll: u0 {tuple(u0.shape)} does not match u {tuple(u.shape)}")
+    return _UnrollDev.apply(u, u0, coef, int(steps), bool(clamp), with_mu)
+
+
 def unroll(u: torch.Tensor, refine: Optional[PDERefine] = None, *, steps: Optional[int] = None, D=None, k=None,
-           a=None, mu=0.0, dt=None, clamp: bool = True, u0: Optional[torch.Tensor] = None) -> torch.Tensor:
+           a=None, mu=0.0, dt=None, clamp: bool = True, u0: Optional[torch.Tensor] = None,
+           coef: Optional[torch.Tensor] = None, with_mu: Optional[bool] = None) -> torch.Tensor:
     """``evolve`` as a differentiable layer: the same arguments without ``threshold``,
     the same bits in the result, ``steps <= UNROLL_MAX_STEPS``, and gradients with respect to ``u``
     and ``u0``: ``unroll_vjp_np`` on the GPU, bit for bit. The forward keeps the state after every
     Tb-th step (``unroll_temporal_block``; ``ceil(steps / Tb) - 1`` maps beside ``u``), the backward
     is one launch per block of Tb steps, last block first, each recomputing its states inside LDS.
     With grad disabled, or when neither ``u`` nor ``u0`` requires grad, it is exactly one ``evolve``
-    call and keeps nothing. The PDE's coefficients take no gradient. No host synchronisation; bad
-    arguments raise ValueError before any GPU work."""
+    call and keeps nothing. Given as Python scalars or a PDERefine, the PDE's coefficients take no
+    gradient. No host synchronisation; bad arguments raise ValueError before any GPU work.
+
+    ``coef``: the five coefficients as a (5,) float32 CUDA tensor in ``COEF_NAMES`` order,
+    in place of ``refine`` and of ``D, k, a, mu, dt``; ``steps``, ``clamp`` and ``with_mu`` (whether the
+    ``mu (u0 - c)`` term is formed: the host never reads the tensor) stay host arguments. The kernels
+    read the values from device memory (``pis_pde_unroll_fwd_dev`` / ``_bwd_dev``), the result and the
+    gradients with respect to ``u`` and ``u0`` are those of the same float32 values given as scalars,
+    bit for bit, and ``coef`` receives its gradient when it requires one: ``unroll_coef_vjp_np``'s
+    sums over the batch, to the order of a float64 sum, bitwise reproducible. The VALUES ARE NOT
+    CHECKED, which would be a host synchronisation: no value can fault a kernel, but values outside
+    the ranges ``evolve_np`` refuses give a map without meaning. ``LearnablePDELayer`` builds them in
+    range."""
+    if coef is not None or with_mu is not None:
+        if coef is None:
+            raise ValueError("unroll: with_mu belongs to coef")
+        return _unroll_dev(u, u0, coef, steps, clamp, with_mu, refine,
+                           D is not None or k is not None or a is not None or mu != 0.0 or dt is not None)
     if refine is not None:
         if not isinstance(refine, PDERefine):
             raise TypeError(f"unroll: refine must be a PDERefine, got {type(refine).__name__}")
@@ -533,17 +754,121 @@ class PDELayer(nn.Module):
         return repr(self.refine)
 
 
+LEARNABLE_NAMES = ("D", "k", "a", "mu", "eps")
+_THETA_MAX = 30.0          # exp(+-30) keeps every product finite and positive in float32
+_LOGIT_MAX = 15.0          # sigmoid(+-15) is the last float32 strictly inside (0, 1) by a margin: 3.1e-7 from the ends
+_STEP_FRACTION_MAX = float(_f32(1.0 - 2.0 ** -21))
+
+
+class LearnablePDELayer(nn.Module):
+    """``unroll`` whose coefficients are trained: ``forward(u) = unroll(u, coef=
+    self.coefficients(), steps=refine.steps, clamp=refine.clamp, with_mu=refine.mu != 0)``.
+
+    ``refine`` gives the initial values D0, k0, a0, mu0 and the step count; ``learn`` names what is
+    trained, each name one 0-dim parameter ``theta[name]`` that starts at 0::
+
+        D  = D0 exp(theta_D)      k = k0 exp(theta_k)      mu = mu0 exp(theta_mu)
+        a  = sigmoid(logit(a0) + theta_a)
+        "eps" (instead of "D" and "k"): D = D0 exp(theta_eps), k = k0 exp(-theta_eps), the tie of the
+                  phase-field preset D = eps, k = 4 / eps
+        dt = s / ((4 D + k) + mu)
+
+    in torch float32 operations on the parameters' device, a coefficient that is not learned being its
+    initial value. ``s`` is the fraction of the monotonicity bound the step keeps: ``step_fraction``
+    (in (0, 1]) when given, else ``dt0 (4 D0 + k0 + mu0)`` when ``refine.dt`` is given, else 0.5, and
+    at most ``1 - 2^-21``, so that the three float32 roundings of ``dt`` cannot carry
+    ``dt (4 D + k + mu)`` past 1. ``theta`` enters through ``clamp(theta, -30, 30)`` and the logit
+    through ``clamp(., -15, 15)`` (no gradient beyond), so D, k, mu stay positive and finite, ``a``
+    strictly inside (0, 1) and ``dt`` positive: every reachable value passes ``_check_evolve``. THIS
+    CONSTRUCTION IS THE RANGE CHECK OF THE DEVICE PATH, which makes none of its own.
+
+    Autograd takes the kernel's five gradients back to ``theta``, the dependence of ``dt`` on D, k
+    and mu included. ValueError: an unknown or repeated name, "eps" beside "D" or "k", a name whose
+    initial value is 0 (its exponential form cannot leave 0), ``a0`` within 3.1e-7 of 0 or 1 when
+    "a" is learned, ``4 D0 + k0 + mu0 = 0``, a ``step_fraction`` outside (0, 1]."""
+
+    def __init__(self, refine: PDERefine, learn=("D", "k", "a"), step_fraction: Optional[float] = None):
+        super().__init__()
+        if not isinstance(refine, PDERefine):
+            raise TypeError(f"LearnablePDELayer: a PDERefine is needed, got {type(refine).__name__}")
+        steps, D0, k0, a0, mu0, dt0 = _check_unroll(refine.steps, refine.D, refine.k, refine.a, refine.mu, refine.dt)
+        learn = (learn,) if isinstance(learn, str) else tuple(learn)
+        for name in learn:
+            if name not in LEARNABLE_NAMES:
+                raise ValueError(f"LearnablePDELayer: cannot learn {name!r}: one of {LEARNABLE_NAMES} is needed")
+        if len(set(learn)) != len(learn) or not learn:
+            raise ValueError(f"LearnablePDELayer: learn = {learn!r}: at least one name, each once, is needed")
+        if "eps" in learn and ("D" in learn or "k" in learn):
+            raise ValueError('LearnablePDELayer: "eps" ties D and k: it cannot stand beside "D" or "k"')
+        zero = [n for n, v in (("D", D0), ("k", k0), ("mu", mu0)) if v == 0 and (n in learn or (n != "mu" and "eps" in learn))]
+        if zero:
+            raise ValueError(f"LearnablePDELayer: {zero} start at 0 and cannot be learned: D0 exp(theta) stays 0")
+        rate0 = 4.0 * float(D0) + float(k0) + float(mu0)
+        if not rate0 > 0:
+            raise ValueError("LearnablePDELayer: 4 D + k + mu > 0 is needed")
+        logit0 = float(np.log(float(a0)) - np.log1p(-float(a0)))
+        if "a" in learn and abs(logit0) > _LOGIT_MAX:
+            raise ValueError(f"LearnablePDELayer: a = {a0} is too close to 0 or 1 to be learned")
+        if step_fraction is not None:
+            if not 0 < float(step_fraction) <= 1:
+                raise ValueError(f"LearnablePDELayer: step_fraction = {step_fraction!r}: (0, 1] is needed")
+            s = float(step_fraction)
+        else:
+            s = 0.5 if refine.dt is None else float(dt0) * rate0
+        self.refine, self.learn = refine, learn
+        self.step_fraction = min(s, _STEP_FRACTION_MAX)
+        self.with_mu = bool(mu0 != 0)
+        self.theta = nn.ParameterDict({name: nn.Parameter(torch.zeros((), dtype=torch.float32)) for name in learn})
+        # D0, k0, a0, mu0, logit(a0), s: device constants, so that coefficients() copies nothing from the host
+        self.register_buffer("_init", torch.tensor([float(D0), float(k0), float(a0), float(mu0), logit0,
+                                                    self.step_fraction], dtype=torch.float32), persistent=False)
+
+    def _scale(self, name: str, sign: float = 1.0) -> torch.Tensor:
+        return torch.exp(sign * self.theta[name].clamp(-_THETA_MAX, _THETA_MAX))
+
+    def coefficients(self) -> torch.Tensor:
+        """The (5,) float32 tensor D, k, a, mu, dt (``COEF_NAMES``) of the current parameters, on their
+        device and attached to them. No host synchronisation."""
+        D0, k0, a0, mu0, logit0, s = self._init.unbind(0)
+        D, k, a, mu = D0, k0, a0, mu0
+        if "eps" in self.learn:
+            D, k = D0 * self._scale("eps"), k0 * self._scale("eps", -1.0)
+        if "D" in self.learn:
+            D = D0 * self._scale("D")
+        if "k" in self.learn:
+            k = k0 * self._scale("k")
+        if "mu" in self.learn:
+            mu = mu0 * self._scale("mu")
+        if "a" in self.learn:
+            a = torch.sigmoid((logit0 + self.theta["a"]).clamp(-_LOGIT_MAX, _LOGIT_MAX))
+        dt = s / ((4.0 * D + k) + mu)  # _check_evolve's order
+        return torch.stack([D, k, a, mu, dt])
+
+    def snapshot(self) -> PDERefine:
+        """The current coefficients as a PDERefine with a concrete ``dt`` (one device-to-host copy: a
+        synchronisation; meant for the end of training and for logs)."""
+        D, k, a, mu, dt = (float(v) for v in self.coefficients().detach().cpu().tolist())
+        return PDERefine(steps=self.refine.steps, D=D, k=k, a=a, mu=mu, dt=dt, clamp=self.refine.clamp)
+
+    def forward(self, u: torch.Tensor) -> torch.Tensor:
+        return unroll(u, coef=self.coefficients(), steps=self.refine.steps, clamp=self.refine.clamp, with_mu=self.with_mu)
+
+    def extra_repr(self) -> str:
+        return f"{self.refine!r}, learn={self.learn!r}, step_fraction={self.step_fraction!r}"
+
+
 class RefinedModel(nn.Module):
     """``forward(x) = PDELayer(refine)(model(x))``: the network whose output is the evolved map, so a
     loss on it reaches the weights through the unrolled steps. The U-Net stays reachable (and
     checkpointed) as ``.model``. There is deliberately no ``forward_with_loss``: the training loop
     then takes the two calls, the model and the criterion on the evolved map, and the fused
-    head + loss path is left only while the layer is on."""
+    head + loss path is left only while the layer is on. Given a ``LearnablePDELayer`` instead of a
+    PDERefine, that module is the layer and its parameters are ``layer.theta.*``."""
 
-    def __init__(self, model: nn.Module, refine: PDERefine):
+    def __init__(self, model: nn.Module, refine: Union[PDERefine, "LearnablePDELayer"]):
         super().__init__()
         self.model = model
-        self.layer = PDELayer(refine)
+        self.layer = refine if isinstance(refine, LearnablePDELayer) else PDELayer(refine)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.layer(self.model(x))
@@ -673,4 +998,6 @@ def create_pde_regularization(diffusion_coeff: float = 1.0, reaction_threshold: 
 __all__ = ["PDERegularization", "create_pde_regularization", "PDERefine", "evolve", "evolve_np", "energies",
            "energies_np", "evolve_temporal_block", "EVOLVE_TILE", "EVOLVE_T_VALUES", "add_refine_flags",
            "refine_from_args", "refine_flags", "unroll", "unroll_vjp_np", "unroll_temporal_block", "PDELayer",
-           "RefinedModel", "UNROLL_TB_VALUES", "UNROLL_MAX_STEPS"]
+           "RefinedModel", "UNROLL_TB_VALUES", "UNROLL_MAX_STEPS", "COEF_NAMES", "unroll_coef_vjp_np",
+           "LearnablePDELayer", "refine_from_file", "LEARNABLE_NAMES",
+           "add_learn_flags", "learn_from_args"]

@@ -486,6 +486,39 @@ def _cached_loaders(train_ds, val_ds, batch_size: int, world: int, rank: int, de
 _REPO_ROOT = Path(__file__).resolve().parent.parent
 
 
+class _WithCoefficientAdam:
+    """The fused ``AdamW`` of a stage with a ``torch.optim.Adam`` for the PDE layer's coefficients
+    beside it: the fused optimizer owns one arena, the U-Net's, and a second arena for
+    a handful of scalars would be a second set of launches for nothing. ``zero_grad`` and ``step``
+    call both; every other attribute is the fused optimizer's, so ``max_grad_norm``,
+    ``skip_nonfinite``, the EMA and the gradient statistics act on the U-Net's arena alone. A
+    coefficient gradient vector with an Inf or a NaN in it is replaced by zeros on the device before
+    the Adam step (``torch.where`` on its finiteness: no host synchronisation)."""
+
+    def __init__(self, fused, adam):
+        self.__dict__["_fused"], self.__dict__["_adam"] = fused, adam
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["_fused"], name)
+
+    def __setattr__(self, name, value):
+        setattr(self._fused, name, value)
+
+    def zero_grad(self, *args, **kwargs):
+        self._fused.zero_grad(*args, **kwargs)
+        self._adam.zero_grad(set_to_none=True)
+
+    def step(self, *args, **kwargs):
+        out = self._fused.step(*args, **kwargs)
+        grads = [p.grad for g in self._adam.param_groups for p in g["params"] if p.grad is not None]
+        if grads:
+            ok = torch.isfinite(torch.stack([g.reshape(()) for g in grads])).all()
+            for g in grads:
+                g.copy_(torch.where(ok, g, torch.zeros_like(g)))
+            self._adam.step()
+        return out
+
+
 def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff: float = 5.0,
           reaction_threshold: float = 0.5, phase_field_weight: float = 1e-4, epsilon: float = 0.05,
           batch_size: int = 8, learning_rate: float = 1e-4, stage1_epochs: int = 50, stage2_epochs: int = 50,
@@ -493,7 +526,8 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
           base_dir: Optional[str] = None, synthetic: Optional[Tuple[int, int, int, int]] = None,
           num_workers: int = 2, device_data: bool = True, device_cache: bool = False,
           augment=None, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
-          ema_decay: Optional[float] = None, ema_warmup: bool = True, pde_layer=None):
+          ema_decay: Optional[float] = None, ema_warmup: bool = True, pde_layer=None,
+          pde_layer_learn: Optional[Tuple[str, ...]] = None, pde_layer_lr: Optional[float] = None):
     """Two-stage training (src/train.py:531-915), same control flow: Stage I (Dice+BCE) always
     runs and saves models/unet_baseline.pth; then either Stage II (PDE loss at lr x 0.1) ->
     unet_pde_regularized.pth, or, with ``use_two_stage=False``, a PDE-loss run at the full lr for
@@ -528,13 +562,32 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
     is untouched. The checkpoints stay the inner U-Net's state dicts under the same names; that
     stage's model is evaluated on the test set with ``refine=pde_layer``, and rank 0 writes the
     layer's parameters to output/pde_layer_<stamp>.json and prints the ``predict.py --refine`` flags
-    that apply the same refinement at inference."""
+    that apply the same refinement at inference.
+
+    ``pde_layer_learn`` (names out of ``pde.LEARNABLE_NAMES``, off by default) makes that
+    layer a ``pde.LearnablePDELayer(pde_layer, learn=pde_layer_learn)``: the named coefficients start
+    at ``pde_layer``'s values and are trained with the weights, by a ``torch.optim.Adam`` of their own
+    at ``pde_layer_lr`` (default: the stage's learning rate; a choice) beside the fused ``AdamW``.
+    ``max_grad_norm``, ``skip_nonfinite`` and the EMA act on the U-Net alone. Rank 0 then writes the
+    initial values to output/pde_layer_<stamp>_initial.json and, at the end of the stage, the learned
+    ones to output/pde_layer_<stamp>.json (``PDERefine(**file)``; ``predict.py --refine-file``), the
+    test-set evaluation refines with the learned values, and the checkpoints stay the U-Net's. Data
+    parallel training of the coefficients is not implemented: ValueError with more than one rank."""
     if augment is not None and not device_cache:
         raise ValueError("augment needs device_cache=True (the cache kernels apply it)")
     if pde_layer is not None:
         from .pde import PDELayer
         PDELayer(pde_layer)  # TypeError / ValueError before any work
+    if pde_layer_learn is not None:
+        if pde_layer is None:
+            raise ValueError("pde_layer_learn needs pde_layer: the initial coefficients and the step count")
+        from .pde import LearnablePDELayer
+        LearnablePDELayer(pde_layer, learn=pde_layer_learn)  # TypeError / ValueError before any work
+    if pde_layer_lr is not None and (pde_layer_learn is None or not pde_layer_lr > 0):
+        raise ValueError("pde_layer_lr: a positive rate, with pde_layer_learn, is needed")
     rank, local_rank, world = init_from_env()
+    if pde_layer_learn is not None and world > 1:
+        raise ValueError("pde_layer_learn: the coefficients' gradients are not all-reduced yet: one rank is needed")
     if not torch.cuda.is_available():
         raise _hip.HipError("train(): the MI355X path needs a GPU (no CPU fallback in this build)")
     device = torch.device("cuda", local_rank)
@@ -598,6 +651,9 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
                     max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
                     ema_warmup=ema_warmup)
         opts.append(opt)
+        if learned:  # the PDE stage with learnable coefficients: their own Adam beside the fused step
+            opt = _WithCoefficientAdam(opt, torch.optim.Adam(learned[0].parameters(),
+                                                             lr=lr if pde_layer_lr is None else pde_layer_lr))
         stopper = EarlyStopping(patience=early_stopping_patience, min_delta=1e-4, mode="max")
         return train_stage(model if net is None else net, train_loader, val_loader, criterion, opt, device,
                            num_epochs=epochs, stage_name=name, early_stopping=stopper, verbose=True, csv_path=csv_path)
@@ -607,6 +663,20 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         if pde_layer is None:
             return None
         from .pde import RefinedModel, refine_flags
+        if pde_layer_learn is not None:
+            from .pde import LearnablePDELayer
+            layer = LearnablePDELayer(pde_layer, learn=pde_layer_learn).to(device)
+            learned.append(layer)
+            first = layer.snapshot()
+            say(f"  PDE layer: {pde_layer.steps} unrolled steps, learning {', '.join(layer.learn)} from D = {first.D}, "
+                f"k = {first.k}, a = {first.a}, mu = {first.mu}, dt = {first.dt} (a fraction {layer.step_fraction:g} of "
+                f"the stability bound), clamp = {first.clamp}")
+            sidecar = out_dir / f"pde_layer_{stamp}_initial.json"
+            if is_main:
+                with open(sidecar, "w") as fh:
+                    json.dump(first.kwargs(), fh, indent=2)
+            say(f"  PDE layer initial parameters saved to: {sidecar}")
+            return RefinedModel(model, layer)
         say(f"  PDE layer: {pde_layer.steps} unrolled steps, D = {pde_layer.D}, k = {pde_layer.k}, a = {pde_layer.a}, "
             f"mu = {pde_layer.mu}, dt = {pde_layer.dt}, clamp = {pde_layer.clamp}")
         sidecar = out_dir / f"pde_layer_{stamp}.json"
@@ -620,7 +690,26 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
             say("  The same refinement at inference: Predictor(refine=PDERefine(**<that file>))")
         return RefinedModel(model, pde_layer)
 
+    def pde_learned():
+        """After the PDE stage: the learned coefficients, written and printed; what the evaluation refines with."""
+        if not learned:
+            return pde_layer
+        from .pde import refine_flags
+        got = learned[0].snapshot()
+        say(f"  PDE layer learned: D = {got.D}, k = {got.k}, a = {got.a}, mu = {got.mu}, dt = {got.dt}")
+        sidecar = out_dir / f"pde_layer_{stamp}.json"
+        if is_main:
+            with open(sidecar, "w") as fh:
+                json.dump(got.kwargs(), fh, indent=2)
+        say(f"  PDE layer parameters saved to: {sidecar}")
+        try:
+            say(f"  The same refinement at inference: predict.py {refine_flags(got)}")
+        except ValueError:
+            say(f"  The same refinement at inference: predict.py --refine-file {sidecar}")
+        return got
+
     opts: List[AdamW] = []  # the stages' optimizers; the last one holds the final average
+    learned: list = []      # the LearnablePDELayer of the PDE stage, once it exists
 
     def save_ema(path):
         """The stage's averaged weights as a plain state dict next to the raw ones (rank 0)."""
@@ -681,6 +770,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
                 say("\nPDE regularization effect:")
                 say(f"  Dice score improvement: {best2['val']['dice_score'] - best1['val']['dice_score']:+.6f}")
         say(f"Stage II metrics saved to: {csv2}")
+        final_refine = pde_learned()
         final_path = models_dir / "unet_pde_regularized.pth"
     else:
         say("\n" + "=" * 70 + "\nSINGLE-STAGE TRAINING (PDE from start)\n" + "=" * 70)
@@ -689,6 +779,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         best, ep, hist = run(pde_loss(), learning_rate, stage1_epochs, "Training", csv1s, net=pde_net())
         result["single"] = (best, ep, hist)
         say(f"Single-stage metrics saved to: {csv1s}")
+        final_refine = pde_learned()
         final_path = models_dir / "unet_pde_regularized.pth"
     if is_main:
         torch.save(model.state_dict(), final_path)
@@ -704,7 +795,7 @@ def train(use_two_stage: bool = True, pde_weight: float = 1e-4, diffusion_coeff:
         with opts[-1].averaged_weights() if ema_decay is not None else contextlib.nullcontext():
             m = evaluate_on_test_set(model, test_dir, test_json, device, batch_size=batch_size, threshold=0.5,
                                      model_name=name, device_cache=device_cache,
-                                     **({} if pde_layer is None else {"refine": pde_layer}))
+                                     **({} if final_refine is None else {"refine": final_refine}))
         tag = "stage2" if use_two_stage else "single_stage"
         save_test_metrics(m, out_dir / f"test_metrics_{tag}_{stamp}{frac}", model_name=name)
         result["test"] = m
