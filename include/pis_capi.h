@@ -267,9 +267,9 @@ int pis_version(void);
                                  (1) and 158.3 (0); one set pixel in a corner of 2048^2 takes 421.9 / 458.2 /
                                  3247.5 us (tools/bench_surface.py, profiles/surface_metrics.txt) */
 #define PIS_TUNE_CONVT_WGRAD_TILE 56 /* pis_convt2x2_wgrad (csrc/wgrad.hip): 1 (default) the fp16x3 kernel on 256 x 128
-                                 block tiles (256 columns (i, j, o) of dy x 128 input channels; a K-step of 32
-                                 pixels is staged once per tile, about 512 blocks, chains of 512 .. 8192 pixels)
-                                 where key 13 = 4, W % 32 == 0, Cin % 128 == 0, (4 Cout) % 256 == 0, the strides
+                                 block tiles (wgrad_h3t_tile_kernel<false, UP2>: 256 columns (i, j, o) of dy x 128
+                                 input channels; a K-step of 32 pixels is staged once per tile, about 512 blocks,
+                                 chains of 512 .. 8192 pixels) where key 13 = 4, W % 32 == 0, Cin % 128 == 0, (4 Cout) % 256 == 0, the strides
                                  are multiples of 4 and the operands 16-B aligned; 0: the 128 x 128 row-staged
                                  kernel (Cin >= 256) and the column-staged bf16x6 kernel, as every other shape.
                                  The key may change between any two calls: pis_convt2x2_wgrad_ws is the maximum
@@ -287,9 +287,9 @@ int pis_version(void);
                                  passes tb explicitly (pde.py does) */
 #define PIS_TUNE_WINO_WGRAD_TILE 58 /* pis_conv3x3_wgrad / _wgrad_keep, the Winograd weight gradient's batched GEMM
                                  (csrc/wgrad.hip): the fp16x3 row-staged kernel on 256 x 128 block tiles
-                                 (wgrad_h3t_tile_kernel: 256 columns of E x 128 of V where Cout % 256 == 0, else
-                                 128 x 256; a K-step's 32 rows are staged once per tile). Contract: T = B (H/m)
-                                 (W/m) tiles with T % 32 == 0 and T >= 512, Cin and Cout multiples of 128 and one
+                                 (wgrad_h3t_tile_kernel<WB>, key 56's kernel on the plain operands: 256 columns of
+                                 E x 128 of V where Cout % 256 == 0, else 128 x 256; a K-step's 32 rows are staged
+                                 once per tile). Contract: T = B (H/m) (W/m) tiles with T % 32 == 0 and T >= 512, Cin and Cout multiples of 128 and one
                                  of them of 256, keys 14 >= 2 and 31 != 0, 16-byte aligned operands. 0: never (the
                                  128 x 128 kernels and bf16x6, as every shape outside the contract); 1 (default):
                                  the shapes the planner's measured rule names (csrc/conv3x3_plan.hip

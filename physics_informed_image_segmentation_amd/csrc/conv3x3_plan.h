@@ -25,7 +25,8 @@ enum class WgradKernel {
   H3T,        // wgrad_h3t_kernel: fp16x3, operands staged by rows, 128 x 128 tiles
   H3T_EXACT,  // ... its form for whole K-steps and 31-bit row offsets (h3t_exact)
   H3T_TWIN,   // ... its timing twin (pis_tune key 2, wrong results)
-  H3T_TILE,   // wgrad_h3t_tile_kernel: the Winograd weight gradient on 256 x 128 (bm = 256) or 128 x 256 tiles
+  H3T_TILE,   // wgrad_h3t_tile_kernel: the Winograd weight gradient on 256 x 128 (bm = 256) or 128 x 256 tiles,
+              // the transposed-conv one (a_up2) on 256 x 128
 };
 constexpr int WT_BK = 32;  // pixels per K-step of the row-staged kernels
 // what the choice needs to know about a launch's operands A (rows lda) and B (rows ldb)

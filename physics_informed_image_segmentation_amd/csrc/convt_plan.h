@@ -7,7 +7,7 @@
 
 namespace pis {
 
-constexpr int WU_BM = 256, WU_BN = 128;  // block tile of wgrad_up2_tile_kernel (wgrad.hip)
+constexpr int WU_BM = 256, WU_BN = 128;  // block tile of wgrad_h3t_tile_kernel<false, UP2> (wgrad.hip)
 
 enum ConvtAlgo {  // forward / input gradient
   CONVT_NONE = 0,
@@ -19,7 +19,7 @@ enum ConvtAlgo {  // forward / input gradient
 };
 enum ConvtWgradAlgo {
   CONVT_WGRAD_NONE = 0,
-  CONVT_WGRAD_TILE,      // wgrad_up2_tile_kernel, 256 x 128 tiles
+  CONVT_WGRAD_TILE,      // wgrad_h3t_tile_kernel<false, UP2>, 256 x 128 tiles
   CONVT_WGRAD_ROWS_UP2,  // wgrad_h3t_kernel<UP2>, row-staged 128 x 128 tiles
   CONVT_WGRAD_SPLITK,    // the generic split-K kernels (choose_wgrad_kernel)
 };
@@ -55,7 +55,7 @@ struct ConvtWgradCall {
 };
 struct ConvtWgradChoice {
   ConvtWgradAlgo algo;
-  WgradKernel kernel;  // CONVT_WGRAD_ROWS_UP2 (its UP2 form) and CONVT_WGRAD_SPLITK
+  WgradKernel kernel;  // run_wgrad's, on a_up2 operands (CONVT_WGRAD_TILE: H3T_TILE)
   WgradPlan pl;
 };
 ConvtWgradChoice resolve_convt_wgrad(const ConvtPlan& p, const ConvtWgradCall& c);

@@ -5,7 +5,7 @@
 namespace pis {
 namespace {
 
-// wgrad_up2_tile_kernel: one resident generation of about 512 blocks, chains of 512 .. 8192 pixels
+// wgrad_h3t_tile_kernel<false, UP2>: one resident generation of about 512 blocks, chains of 512 .. 8192 pixels
 WgradPlan plan_convt_tile(int Mp, int Np, int P) {
   WgradPlan p{};
   p.bm = WU_BM;
@@ -66,7 +66,7 @@ ConvtAlgo resolve_convt(const ConvtPlan& p, const ConvtCall& c) {
 
 ConvtWgradChoice resolve_convt_wgrad(const ConvtPlan& p, const ConvtWgradCall& c) {
   const bool vec = c.ldx % 4 == 0 && c.lddy % 4 == 0 && c.aligned16;  // float4 rows of x and dy
-  if (p.tile.shape && p.tile.wanted && vec) return {CONVT_WGRAD_TILE, WgradKernel::H3T, p.tile.pl};
+  if (p.tile.shape && p.tile.wanted && vec) return {CONVT_WGRAD_TILE, WgradKernel::H3T_TILE, p.tile.pl};
   WgradOperands o{};
   o.plain = true; o.a_up2 = true; o.W = p.W; o.P = p.B * p.H * p.W; o.Np = p.Cin;
   o.lda = c.lddy; o.ldb = c.ldx; o.aligned16 = c.aligned16;

@@ -1011,8 +1011,7 @@ constexpr int WT_BUF = 4 * WT_PLANE;             // A hi, A lo, B hi, B lo
 
 __device__ __forceinline__ int wtsw(int row, int chunk) { return row * 128 + 8 * (chunk ^ ((row & 3) << 2)); }
 
-// ---- pieces shared by the row-staged kernels (wgrad_h3t_kernel, wgrad_up2_tile_kernel,
-// wgrad_h3t_tile_kernel) ----
+// ---- pieces shared by the two row-staged kernels (wgrad_h3t_kernel, wgrad_h3t_tile_kernel) ----
 // (their transposed fragment read, accumulator re-expression and slab epilogue stay written out in
 // each: as shared functions they changed the kernels' code, profiles/convt_plan_codegen.txt)
 __device__ __forceinline__ float umax4(const float (&r)[4]) {  // r >= 0: bit-pattern max
@@ -1036,7 +1035,7 @@ __device__ __forceinline__ f32x16 h3_mfma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 b
 // operand row offset fits 31 bits: no per-row tail test, and the plain operands are read by
 // buffer loads from the block's base (32-bit lane offset + a wave-uniform row offset per j)
 // instead of 64-bit per-lane address arithmetic. Same loads, same sums (bitwise equal).
-template <bool UP2 = false, int D = 2, bool TW = false, bool EX = false>
+template <bool UP2 = false, bool TW = false, bool EX = false>
 __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   const Remap2 rm = xcd_remap2();
   if (rm.batch) {
@@ -1072,14 +1071,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   const bool do_bias = g.part_bias != nullptr && n0 == 0 && rm.batch == g.bias_xi;
   f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
 
-  f32x4 ra[D][4], rb[D][4];
+  f32x4 ra[2][4], rb[2][4];
   // EX: buffer resources at the block's column bases; lane offsets of row p_begin + srow
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.a + m0), (short)0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.b + n0), (short)0, 0x7fffffff, 0x00020000);
   const uint32_t la0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.lda + 4u * sc4);
   const uint32_t lb0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.ldb + 4u * sc4);
   auto gload = [&](f32x4 (&xa)[4], f32x4 (&xb)[4], int st) __attribute__((always_inline)) {
-    if (TW && (g.dbg & 1) && st >= D) return;
+    if (TW && (g.dbg & 1) && st >= 2) return;
     if constexpr (EX) {  // rows p_begin + 32 st + srow + 8 j, all inside the split
       const uint32_t ra_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.lda, rb_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.ldb;
       size_t abase = 0;
@@ -1174,22 +1173,21 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   float ua = 0.f, ub = 0.f;
   float s_a[2] = {0.f, 0.f}, s_b[2] = {0.f, 0.f};  // per buffer parity: the staged K-step's scales
 
-  // D register sets: the raw operands of K-step st + D in flight while K-step st multiplies. Set
-  // of K-step k: k % D; LDS buffer: k & 1. (D = 3 measured neutral on every C2 layer,
-  // profiles/r3_q22_wgrad_depth.txt: D = 2 is launched.)
+  // Two register sets: the raw operands of K-step st + 2 in flight while K-step st multiplies.
+  // Register set and LDS buffer of K-step k: k & 1. (A third set measured neutral on every C2
+  // layer, profiles/r3_q22_wgrad_depth.txt.)
   if (nst > 0) {
 #pragma unroll
-    for (int k = 0; k < D; ++k)
+    for (int k = 0; k < 2; ++k)
       if (k < nst) gload(ra[k], rb[k], k);
     publish(ra[0], rb[0], 0);
     __syncthreads();
     split_store(ra[0], rb[0], 0, s_a[0], s_b[0]);
-    if (nst > D) gload(ra[0], rb[0], D);
+    if (nst > 2) gload(ra[0], rb[0], 2);
   }
-  auto kstep = [&](int st, auto par_c, auto set_c) __attribute__((always_inline)) {
-    constexpr int cur = decltype(par_c)::value, nxt = cur ^ 1;
-    constexpr int sn = (decltype(set_c)::value + 1) % D;  // register set of K-step st + 1
-    if (st + 1 < nst) publish(ra[sn], rb[sn], nxt);
+  auto kstep = [&](int st, auto par_c) __attribute__((always_inline)) {
+    constexpr int cur = decltype(par_c)::value, nxt = cur ^ 1;  // K-step st + 1: buffer and register set nxt
+    if (st + 1 < nst) publish(ra[nxt], rb[nxt], nxt);
     __syncthreads();  // buffer cur staged; buffer nxt's readers (K-step st - 1) done
     const _Float16* buf = smem + cur * WT_BUF;
     f16x8 af[2][2], bf[2][2];
@@ -1201,8 +1199,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
         bf[pl][a] = frag(buf + (2 + pl) * WT_PLANE, 0, 64 * wn + 32 * a);
       }
     if (st + 1 < nst) {
-      if (!(TW && (g.dbg & 2) && st > 0)) split_store(ra[sn], rb[sn], nxt, s_a[nxt], s_b[nxt]);
-      if (st + 1 + D < nst) gload(ra[sn], rb[sn], st + 1 + D);
+      if (!(TW && (g.dbg & 2) && st > 0)) split_store(ra[nxt], rb[nxt], nxt, s_a[nxt], s_b[nxt]);
+      if (st + 3 < nst) gload(ra[nxt], rb[nxt], st + 3);
     }
     {  // the partial sums in this K-step's units (exact: powers of two, one factor at a time)
       const float sa = s_a[cur], sb = s_b[cur];
@@ -1235,25 +1233,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
         for (int b = 0; b < 2; ++b) acc[a][b] = h3_mfma3(af[0][a], af[1][a], bf[0][b], bf[1][b], acc[a][b]);
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  if constexpr (D == 2) {
 #pragma unroll 1
-    for (int st = 0; st < nst; st += 2) {
-      kstep(st, I0{}, I0{});
-      if (st + 1 < nst) kstep(st + 1, I1{}, I1{});
-    }
-  } else {  // K-steps by six: buffer parity and register set both repeat
-#pragma unroll 1
-    for (int st = 0; st < nst; st += 6) {
-      kstep(st, I0{}, I0{});
-      if (st + 1 < nst) kstep(st + 1, I1{}, I1{});
-      if (st + 2 < nst) kstep(st + 2, I0{}, I2{});
-      if (st + 3 < nst) kstep(st + 3, I1{}, I0{});
-      if (st + 4 < nst) kstep(st + 4, I0{}, I1{});
-      if (st + 5 < nst) kstep(st + 5, I1{}, I2{});
-    }
+  for (int st = 0; st < nst; st += 2) {
+    kstep(st, std::integral_constant<int, 0>{});
+    if (st + 1 < nst) kstep(st + 1, std::integral_constant<int, 1>{});
   }
   float* out = g.part + (size_t)split * (g.split_stride ? g.split_stride : (int64_t)g.Mp * g.Np);
   const float inv_a = ua != 0.f ? 1.f / ua : 0.f, inv_b = ub != 0.f ? 1.f / ub : 0.f;
@@ -1293,215 +1276,42 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_kernel(WgradArgs g) {
   }
 }
 
-// The transposed-conv weight gradient on 256 x 128 tiles (pis_tune key 56): wgrad_h3t_kernel<UP2>'s
-// contraction, fp16x3 with one power-of-two scale per operand and K-step, on a block tile of 256
-// columns of A (for 128 -> 64 channels all four taps x 64 output channels: one block owns the whole
-// dW) x 128 input channels, so a K-step's 32 pixels of x are staged once per 256 columns of A and
-// its dy rows once per 128 input channels, and 512 blocks (one resident generation at two per CU)
-// already give chains of 512 .. 1024 pixels at the training shapes (67 MB of slabs per layer; the
-// 128 x 128 form writes twice that at 256 -> 128 and 512 -> 256 channels). DESIGN §4 round 10.
-// Wave (wm, wn): columns 128 wm .. of A x input channels 64 wn ..: 4 x 2 accumulator blocks of
-// 32 x 32 (128 registers), 24 transposed fragment reads per 48 MFMAs.
-// LDS: ONE K-step, six planes of wgrad_h3t_kernel's [32 pixels][128 columns] layout (wtsw): A hi
-// (columns 0..127, 128..255), A lo (the same), B hi, B lo = 48 KB, two blocks per CU. The raw
-// operands of K-step st + 1 are loaded while K-step st multiplies (one register set) and are split
-// into the planes between the K-step's second barrier and the next one's first; the CU's other
-// block multiplies meanwhile.
+// The row-staged contraction on 256 x 128 tiles: the transposed-conv weight gradient (UP2, pis_tune
+// key 56) and the Winograd weight gradient (key 58). Same arithmetic as wgrad_h3t_kernel: fp16x3,
+// smallest products first, one power-of-two scale per operand and K-step of 32 rows from the
+// block-wide max (h3_keep), the accumulator units kept as two factors. The block tile is 256
+// columns of one operand x 128 of the other, so a K-step's rows of the narrow operand are staged
+// once per 256 columns of the wide one (the 128 x 128 form: once per 128), and a wave's 128 x 64
+// sub-tile (4 x 2 accumulator blocks of 32 x 32, 128 registers) reads 24 transposed fragments per
+// 48 MFMAs instead of 16 per 24.
+// WB = false: the wide operand is A; wave (w0, w1) owns columns 128 w0 .. of A x columns 64 w1 ..
+// of B. WB = true: the wide operand is B; wave (w0, w1) owns columns 64 w1 .. of A x 128 w0 .. of
+// B. Either way A is the MFMA's row operand, so a slab store's 32 lanes run along B's columns (128
+// contiguous bytes).
+// LDS: ONE K-step, six planes of wgrad_h3t_kernel's [32 rows][128 columns] layout (wtsw): A hi,
+// A lo, B hi, B lo with two planes for each of the wide operand's = 48 KB, two blocks per CU; two
+// barriers per K-step. The raw operands of K-step st + 1 are loaded while K-step st multiplies (one
+// register set) and are split into the planes between the K-step's second barrier and the next
+// one's first; the CU's other block multiplies meanwhile. No atomics.
+// UP2 (WB = false only): wgrad_h3t_kernel<UP2>'s operands. A(p, (i, j, o)) = dy at the up-sampled
+// pixel (2y + i, 2x + j) of low-resolution pixel p = (b, y, x), B = x; for 128 -> 64 channels the
+// 256 columns of A are all four taps x 64 output channels: one block owns the whole dW (the plan
+// and what it saves: DESIGN §4 round 10). A K-step's dy rows are two pixels apart from the image
+// row's base, by pointer loads; one launch (1-D grid, no batch offsets), slabs at part + split *
+// Mp * Np, bias partials [split][Mp] by the blocks whose B tile is the first.
 // Needs W % 32 == 0 and pix_per_split % 32 == 0 (every split is whole K-steps of one image row),
 // Mp % 256 == 0, Np % 128 == 0, Ca % 4 == 0, lda / ldb % 4 == 0 and 16-B aligned operands.
+// !UP2: the plain operands A = E[xi][T][Cout], B = V[xi][T][Cin] of the batched launch (one batch
+// per xi, xcd_remap2), read by buffer loads from the block's base in whole K-steps (h3t_exact).
+// WB = false needs Cout % 256 == 0, WB = true Cout = 128 against Cin % 256 == 0. Slabs at part +
+// split * split_stride (+ xi Cout Cin in the base), bias partials [split][Cout] by the blocks of
+// plane bias_xi whose Cin tile is the first.
 constexpr int WU_LDS = 6 * WT_PLANE;  // fp16 elements
 
-__global__ __launch_bounds__(256, 2) void wgrad_up2_tile_kernel(WgradArgs g) {
-  __shared__ __attribute__((aligned(16))) _Float16 smem[WU_LDS];
-  __shared__ float red[2][2][4];  // [K-step parity][A|B][wave] maxima
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave & 1, wn = wave >> 1, li = lane & 31, lh = lane >> 5;
-  const int ntn = g.Np / WU_BN;
-  const int tiles = (g.Mp / WU_BM) * ntn;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = bid / tiles;
-  const int tile = bid - split * tiles;
-  const int m0 = (tile / ntn) * WU_BM, n0 = (tile % ntn) * WU_BN;
-  const int p_begin = split * g.pix_per_split;
-  const int p_end = min(g.P, p_begin + g.pix_per_split);
-  const int nst = max(0, (p_end - p_begin) / WT_BK);
-  // staging: pixel rows srow + 8 j, float4 column sc4 of B and of each 128-column half of A
-  const int srow = tid >> 5, sc4 = tid & 31;
-  const float* gb = g.b + n0 + 4 * sc4;
-  const float* ga[2];  // this thread's column group of half h at dy pixel (i, j) of the image's first 2 x 2 block
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int col = m0 + 128 * h + 4 * sc4, ij = col / g.Ca;
-    ga[h] = g.a + (col - ij * g.Ca) + ((size_t)(ij >> 1) * (2 * g.W) + (ij & 1)) * g.lda;
-  }
-  const bool do_bias = g.part_bias != nullptr && n0 == 0;
-  f32x4 bsum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-
-  f32x4 xa[2][4], xb[4];
-  auto gload = [&](int st) __attribute__((always_inline)) {
-    // the K-step's 32 pixels: image row (b, y), columns x0 .. x0 + 31; A rows two dy pixels apart
-    const int p0 = p_begin + st * WT_BK;
-    const int hw = g.H * g.W, b = p0 / hw, rem = p0 - b * hw, y = rem / g.W, x0 = rem - y * g.W;
-    const size_t abase = (((size_t)b * 2 * g.H + 2 * y) * (2 * g.W) + 2 * x0) * g.lda;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = srow + 8 * j;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) xa[h][j] = *reinterpret_cast<const f32x4*>(ga[h] + abase + (size_t)(2 * r) * g.lda);
-      xb[j] = *reinterpret_cast<const f32x4*>(gb + (size_t)(p0 + r) * g.ldb);
-    }
-  };
-  auto publish = [&](int par) __attribute__((always_inline)) {
-    if (do_bias) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        bsum[0] += xa[0][j];
-        bsum[1] += xa[1][j];
-      }
-    }
-    const float ma = wave_max_nonneg(absmax_x4(xa));
-    const float mb = wave_max_nonneg(absmax_x4(xb));
-    if (lane == 0) {
-      red[par][0][wave] = ma;
-      red[par][1][wave] = mb;
-    }
-  };
-  float sa = 0.f, sb = 0.f, sa_min = __builtin_inff(), sb_min = __builtin_inff();  // the staged K-step's scales
-  auto split_store = [&](int par) __attribute__((always_inline)) {
-    sa = h3_keep(sa, umax4(red[par][0]), sa_min);
-    sb = h3_keep(sb, umax4(red[par][1]), sb_min);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int off = wtsw(srow + 8 * j, sc4 >> 1) + 4 * (sc4 & 1);
-      u32x2 h, l;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        split2h_x4(xa[hf][j] * sa, h, l);
-        *reinterpret_cast<u32x2*>(smem + hf * WT_PLANE + off) = h;
-        *reinterpret_cast<u32x2*>(smem + (2 + hf) * WT_PLANE + off) = l;
-      }
-      split2h_x4(xb[j] * sb, h, l);
-      *reinterpret_cast<u32x2*>(smem + 4 * WT_PLANE + off) = h;
-      *reinterpret_cast<u32x2*>(smem + 5 * WT_PLANE + off) = l;
-    }
-  };
-
-  // transposed-read lane roles, as wgrad_h3t_kernel
-  const int gq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  const int kh = gq >> 1, chk = 2 * (gq & 1) + (pp >> 1), slot = 4 * (pp & 1);
-  auto frag = [&](const _Float16* plane, int ks, int col0) __attribute__((always_inline)) {
-    const int row = 16 * ks + 8 * kh + q, ch = col0 / 8 + chk;
-    const s16x4 lo4 = tr_read(plane + wtsw(row, ch) + slot);
-    const s16x4 hi4 = tr_read(plane + wtsw(row + 4, ch) + slot);
-    return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
-  const _Float16* a_hi = smem + wm * WT_PLANE;
-  const _Float16* a_lo = smem + (2 + wm) * WT_PLANE;
-  const _Float16* b_hi = smem + 4 * WT_PLANE;
-  const _Float16* b_lo = smem + 5 * WT_PLANE;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-  // the partial sums are in units ua * ub, kept as two factors (0: none yet), as wgrad_h3t_kernel
-  float ua = 0.f, ub = 0.f;
-
-  if (nst > 0) {
-    gload(0);
-    publish(0);
-    __syncthreads();
-    split_store(0);
-    if (nst > 1) gload(1);
-  }
-#pragma unroll 1
-  for (int st = 0; st < nst; ++st) {
-    __syncthreads();  // K-step st staged
-    if (sa != ua || sb != ub) {  // the partial sums in this K-step's units (exact: powers of two)
-      if (ua != 0.f) {
-        const float fa = sa / ua, fb = sb / ub;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) acc[a][b] = (acc[a][b] * fa) * fb;
-      }
-      ua = sa;
-      ub = sb;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      f16x8 bf[2][2];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        bf[0][b] = frag(b_hi, ks, 64 * wn + 32 * b);
-        bf[1][b] = frag(b_lo, ks, 64 * wn + 32 * b);
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const f16x8 ah = frag(a_hi, ks, 32 * a), al = frag(a_lo, ks, 32 * a);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = h3_mfma3(ah, al, bf[0][b], bf[1][b], acc[a][b]);
-      }
-    }
-    const bool more = st + 1 < nst;
-    if (more) publish((st + 1) & 1);
-    __syncthreads();  // every wave has read K-step st's fragments
-    if (more) {
-      split_store((st + 1) & 1);
-      if (st + 2 < nst) gload(st + 2);
-    }
-  }
-  float* out = g.part + (size_t)split * g.Mp * g.Np;
-  const float inv_a = ua != 0.f ? 1.f / ua : 0.f, inv_b = ub != 0.f ? 1.f / ub : 0.f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int n = n0 + 64 * wn + 32 * b + li;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + 128 * wm + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        out[(size_t)m * g.Np + n] = (acc[a][b][r] * inv_a) * inv_b;
-      }
-    }
-  if (do_bias) {  // column sums over the block's pixels: the 8 threads of each column group, fixed order
-    f32x4* rb4 = reinterpret_cast<f32x4*>(smem);  // the loop's last barrier is behind every fragment read
-    rb4[tid] = bsum[0];
-    rb4[256 + tid] = bsum[1];
-    __syncthreads();
-    if (tid < 64) {
-      const int base = 256 * (tid >> 5) + (tid & 31);
-      f32x4 t = rb4[base];
-#pragma unroll
-      for (int r = 1; r < 8; ++r) t += rb4[base + 32 * r];
-      *reinterpret_cast<f32x4*>(g.part_bias + (size_t)split * g.Mp + m0 + 4 * tid) = t;
-    }
-  }
-}
-
-// The Winograd weight gradient on 256 x 128 tiles (pis_tune key 58): wgrad_up2_tile_kernel's form
-// for the plain operands A = E[xi][T][Cout], B = V[xi][T][Cin] of the batched launch (one batch
-// per xi, xcd_remap2). Same arithmetic as wgrad_h3t_kernel: fp16x3, smallest products first, one
-// power-of-two scale per operand and K-step of 32 rows from the block-wide max (h3_keep), the
-// accumulator units kept as two factors. The block tile is 256 columns of one operand x 128 of
-// the other, so a K-step's rows of the narrow operand are staged once per 256 columns of the wide
-// one (the 128 x 128 form: once per 128), and a wave's 128 x 64 sub-tile (4 x 2 accumulator
-// blocks) reads 24 transposed fragments per 48 MFMAs instead of 16 per 24.
-// WB = false: the wide operand is A (Cout % 256 == 0); wave (w0, w1) owns output channels
-// 128 w0 .. x input channels 64 w1 ... WB = true: the wide operand is B (Cout = 128 against
-// Cin % 256 == 0); wave (w0, w1) owns output channels 64 w1 .. x input channels 128 w0 ... Either
-// way A is the MFMA's row operand, so a slab store's 32 lanes run along Cin (128 contiguous bytes).
-// LDS: one K-step, six [32][128] planes (wtsw): A hi, A lo, B hi, B lo with two planes for each of
-// the wide operand's = 48 KB, two blocks per CU; two barriers per K-step; the raw operands of
-// K-step st + 1 are loaded (buffer loads from the block's base, whole K-steps: h3t_exact) while
-// K-step st multiplies. Slabs at part + split * split_stride (+ xi Cout Cin in the base), bias
-// partials [split][Cout] by the blocks of plane bias_xi whose Cin tile is the first. No atomics.
-template <bool WB>
+template <bool WB, bool UP2 = false>
 __global__ __launch_bounds__(256, 2) void wgrad_h3t_tile_kernel(WgradArgs g) {
-  const Remap2 rm = xcd_remap2();
+  static_assert(!(WB && UP2), "the transposed-conv operands come with A as the wide operand only");
+  const Remap2 rm = UP2 ? Remap2{0, xcd_remap(blockIdx.x, gridDim.x)} : xcd_remap2();  // UP2: one batch, 1-D grid
   if (rm.batch) {
     g.a += rm.batch * g.bs_a;
     g.b += rm.batch * g.bs_b;
@@ -1525,18 +1335,42 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_tile_kernel(WgradArgs g) {
   const int nst = max(0, (p_end - p_begin) / WT_BK);
   // staging: rows srow + 8 j, float4 column sc4 of each 128-column half
   const int srow = tid >> 5, sc4 = tid & 31;
-  const bool do_bias = g.part_bias != nullptr && n0 == 0 && rm.batch == g.bias_xi;
+  const bool do_bias = g.part_bias != nullptr && n0 == 0 && (UP2 || rm.batch == g.bias_xi);
   f32x4 bsum[HA];
 #pragma unroll
   for (int h = 0; h < HA; ++h) bsum[h] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // buffer resources at the block's column bases; lane offsets of row p_begin + srow
+  // UP2: this thread's column group of B, and of A's half h at dy pixel (i, j) of the image's first 2 x 2 block
+  const float *gb = nullptr, *ga[HA] = {};
+  if constexpr (UP2) {
+    gb = g.b + n0 + 4 * sc4;
+#pragma unroll
+    for (int h = 0; h < HA; ++h) {
+      const int col = m0 + 128 * h + 4 * sc4, ij = col / g.Ca;
+      ga[h] = g.a + (col - ij * g.Ca) + ((size_t)(ij >> 1) * (2 * g.W) + (ij & 1)) * g.lda;
+    }
+  }
+  // !UP2: buffer resources at the block's column bases; lane offsets of row p_begin + srow
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.a + m0), (short)0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.b + n0), (short)0, 0x7fffffff, 0x00020000);
   const uint32_t la0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.lda + 4u * sc4);
   const uint32_t lb0 = 4u * ((uint32_t)(p_begin + srow) * (uint32_t)g.ldb + 4u * sc4);
   f32x4 xa[HA][4], xb[HB][4];
   auto gload = [&](int st) __attribute__((always_inline)) {  // rows p_begin + 32 st + srow + 8 j, all inside the split
+    if constexpr (UP2) {
+      // the K-step's 32 pixels: image row (b, y), columns x0 .. x0 + 31; A rows two dy pixels apart
+      const int p0 = p_begin + st * WT_BK;
+      const int hw = g.H * g.W, b = p0 / hw, rem = p0 - b * hw, y = rem / g.W, x0 = rem - y * g.W;
+      const size_t abase = (((size_t)b * 2 * g.H + 2 * y) * (2 * g.W) + 2 * x0) * g.lda;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = srow + 8 * j;
+#pragma unroll
+        for (int h = 0; h < HA; ++h) xa[h][j] = *reinterpret_cast<const f32x4*>(ga[h] + abase + (size_t)(2 * r) * g.lda);
+        xb[0][j] = *reinterpret_cast<const f32x4*>(gb + (size_t)(p0 + r) * g.ldb);
+      }
+      return;
+    }
     const uint32_t ra_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.lda, rb_s = 4u * (uint32_t)(st * WT_BK) * (uint32_t)g.ldb;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1671,7 +1505,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_tile_kernel(WgradArgs g) {
       if (st + 2 < nst) gload(st + 2);
     }
   }
-  float* out = g.part + (size_t)split * (g.split_stride ? g.split_stride : (int64_t)g.Mp * g.Np);
+  float* out = UP2 ? g.part + (size_t)split * g.Mp * g.Np
+                   : g.part + (size_t)split * (g.split_stride ? g.split_stride : (int64_t)g.Mp * g.Np);
   const float inv_a = ua != 0.f ? 1.f / ua : 0.f, inv_b = ub != 0.f ? 1.f / ub : 0.f;
   const int mw = m0 + (WB ? 64 * w1 : 128 * w0), nw = n0 + (WB ? 128 * w0 : 64 * w1);
 #pragma unroll
@@ -1685,7 +1520,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3t_tile_kernel(WgradArgs g) {
         out[(size_t)m * g.Np + n] = (acc[a][b][r] * inv_a) * inv_b;
       }
     }
-  if (do_bias) {  // column sums of the raw E rows: the 8 threads of each column group, fixed order
+  if (do_bias) {  // column sums of the raw A rows over the block's pixels: the 8 threads of each column group, fixed order
     f32x4* rb4 = reinterpret_cast<f32x4*>(smem);  // the loop's last barrier is behind every fragment read
 #pragma unroll
     for (int h = 0; h < HA; ++h) rb4[256 * h + tid] = bsum[h];
@@ -1721,19 +1556,22 @@ static int run_wgrad(const WgradArgs& base, const WgradPlan& pl, WgradKernel k, 
   static const Kernel h3[4] = {wgrad_h3_kernel<64, 64>, wgrad_h3_kernel<64, 128>, wgrad_h3_kernel<128, 64>,
                                wgrad_h3_kernel<128, 128>};
   const int t = (pl.bm == 128 ? 2 : 0) + (pl.bn == 128 ? 1 : 0);
-  const bool up2 = a.a_up2 != 0;  // the row-staged kernels: 128 x 128 tiles only
+  const bool up2 = a.a_up2 != 0;  // the row-staged kernels: 128 x 128 tiles, or the plan's 256 x 128 / 128 x 256
   Kernel fn = f32[t];
   const char* name = "wgrad_f32";
   switch (k) {
     case WgradKernel::F32: break;
     case WgradKernel::X6: fn = x6[t]; name = "wgrad_x6"; break;
     case WgradKernel::H3_COLS: fn = h3[t]; name = "wgrad_h3"; break;
-    case WgradKernel::H3T: fn = up2 ? wgrad_h3t_kernel<true, 2> : wgrad_h3t_kernel<false, 2>; break;
-    case WgradKernel::H3T_EXACT: fn = up2 ? wgrad_h3t_kernel<true, 2, false, true> : wgrad_h3t_kernel<false, 2, false, true>; break;
-    case WgradKernel::H3T_TWIN: fn = wgrad_h3t_kernel<false, 2, true>; break;
-    case WgradKernel::H3T_TILE: fn = pl.bn == 256 ? wgrad_h3t_tile_kernel<true> : wgrad_h3t_tile_kernel<false>; break;
+    case WgradKernel::H3T: fn = up2 ? wgrad_h3t_kernel<true> : wgrad_h3t_kernel<false>; break;
+    case WgradKernel::H3T_EXACT: fn = up2 ? wgrad_h3t_kernel<true, false, true> : wgrad_h3t_kernel<false, false, true>; break;
+    case WgradKernel::H3T_TWIN: fn = wgrad_h3t_kernel<false, true>; break;
+    case WgradKernel::H3T_TILE:
+      fn = up2 ? wgrad_h3t_tile_kernel<false, true> : pl.bn == 256 ? wgrad_h3t_tile_kernel<true> : wgrad_h3t_tile_kernel<false>;
+      break;
   }
-  if (k >= WgradKernel::H3T) name = k == WgradKernel::H3T_TILE ? "wgrad_h3t_tile" : up2 ? "wgrad_h3t<up2>" : "wgrad_h3t";
+  if (k == WgradKernel::H3T_TILE) name = up2 ? "wgrad_up2_tile" : "wgrad_h3t_tile";
+  else if (k >= WgradKernel::H3T) name = up2 ? "wgrad_h3t<up2>" : "wgrad_h3t";
   hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, a);
   return launch_status(name);
 }
@@ -2068,17 +1906,7 @@ extern "C" int pis_convt2x2_wgrad(const float* x, int ldx, const float* dy, int 
   a.b = x; a.ldb = ldx; a.b_mode = B_PLAIN; a.Cb = Cin;
   a.B = B; a.H = H; a.W = W; a.P = B * H * W; a.Mp = 4 * Cout; a.Np = Cin; a.part = (float*)ws;
   a.part_bias = db ? bias_slabs(ws, pl) : nullptr;
-  int rc = PIS_ERR_ARG;
-  switch (c.algo) {
-    case CONVT_WGRAD_TILE:
-      a.pix_per_split = pl.pps;
-      hipLaunchKernelGGL(wgrad_up2_tile_kernel, dim3((a.Mp / WU_BM) * (a.Np / WU_BN) * pl.splits), dim3(256), 0, s, a);
-      rc = launch_status("wgrad_up2_tile");
-      break;
-    case CONVT_WGRAD_ROWS_UP2:
-    case CONVT_WGRAD_SPLITK: rc = run_wgrad(a, pl, c.kernel, s); break;
-    case CONVT_WGRAD_NONE: break;
-  }
+  int rc = c.algo == CONVT_WGRAD_NONE ? PIS_ERR_ARG : run_wgrad(a, pl, c.kernel, s);
   // weights + bias (slabs [split][i][j][o]: 4 splits slabs of Cout) in one launch
   if (!rc) rc = reduce_slabs2(a.part, pl.splits, (int64_t)a.Mp * a.Np, dw_ijoc, a.part_bias, pl.splits * 4, Cout, db,
                               flags & PIS_ACCUMULATE, s);

@@ -1,5 +1,5 @@
 """The transposed-conv weight gradient on 256 x 128 block tiles (pis_tune key 56, csrc/wgrad.hip
-wgrad_up2_tile_kernel) against float64 on the CPU:
+wgrad_h3t_tile_kernel<false, UP2>) against float64 on the CPU:
 
     dW[i][j][o][c] = sum_p dy[b, 2y+i, 2x+j, o] * x[b, y, x, c],   db[o] = sum dy
 
