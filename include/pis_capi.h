@@ -481,6 +481,14 @@ int pis_debug_convt2x2_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout)
  * (tiles x splits x transform planes) where the pointers are not NULL. */
 int pis_debug_wino_wgrad_kernel(int B, int H, int W, int Cin, int Cout, int aligned);
 int pis_debug_wino_wgrad_plan(int B, int H, int W, int Cin, int Cout, int aligned, int* splits, int* blocks);
+/* Tooling and tests (host only, no GPU): the launch variants the planner (csrc/conv3x3_plan.h) names for the
+ * Winograd forward / input gradient under the current keys. _gemm: the batched NT GEMM of a contraction of C
+ * channels into N outputs (PIS_TUNE_WINO_TILE) — 0 generic implicit GEMM, 1 / 2 / 3 fp32 MFMA 128x256 / 128x128 /
+ * 128x64, 4 / 5 bf16x6 K-step 16 128x128 / 128x64, 6 / 7 bf16x6 K-step 32, 8 / 9 fp16x3 K-step 32 (WinoGemm).
+ * _fused_form: the fused contraction of C = 64 or 128 channels over T tiles (T % 32 == 0) — tile groups per block
+ * G | 16 (fp16x3) | 32 (staggered wave pairs). -1: outside those arguments. */
+int pis_debug_wino_gemm(int N, int C);
+int pis_debug_wino_fused_form(int C, int T);
 /* Tooling and tests: the algorithm the planner (csrc/convt_plan.h) resolves for a call of this shape under the
  * current keys. op 0: pis_convt2x2_fwd with ld_src = ldx, ld_dst = ldy and a bias; op 1: pis_convt2x2_dgrad with
  * ld_src = lddy, ld_dst = lddx = ldm and PIS_MASK; op 2: pis_convt2x2_wgrad with ld_src = ldx, ld_dst = lddy.

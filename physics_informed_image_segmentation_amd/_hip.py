@@ -89,6 +89,8 @@ _SIGNATURES = {
     "pis_convt2x2_wgrad": ([P, I, P, I, P, P, I, I, I, I, I, I, P, Z, P], c_int),
     "pis_debug_convt2x2_wgrad_tile_splits": ([I, I, I, I, I], c_int),
     "pis_debug_convt2x2_algo": ([I, I, I, I, I, I, I, I, I], c_int),
+    "pis_debug_wino_gemm": ([I, I], c_int),
+    "pis_debug_wino_fused_form": ([I, I], c_int),
     "pis_debug_wino_wgrad_kernel": ([I, I, I, I, I, I], c_int),
     "pis_debug_wino_wgrad_plan": ([I, I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)], c_int),
     "pis_maxpool2x2_fwd": ([P, I, P, I, I, I, I, P], c_int),

@@ -91,6 +91,48 @@ enum PrepKind {
   PREP_E_ONLY,    // the overlap-add input gradient (key 51) contracts the weight gradient's E
 };
 
+// ---- the Winograd forward / input gradient's launch variants (winograd.hip launches what these say) ----
+// the batched NT GEMM M_xi = V_xi U_xi^T of the F(m x m) pipelines: one value per instantiation
+enum class WinoGemm {
+  IGEMM,        // the generic implicit GEMM (launch_igemm), any shape
+  F32_256,      // gemm_nt_kernel<128, 256>: fp32 MFMA
+  F32_128,      // gemm_nt_kernel<128, 128>
+  F32_64,       // gemm_nt_kernel<128, 64>
+  X6_128,       // gemm_nt_x6_kernel<128, 128>: bf16x6, K-step 16
+  X6_64,        // gemm_nt_x6_kernel<128, 64>
+  X6_BK32_128,  // gemm_nt_x6_bk32_kernel<128, 128, 3>: bf16x6, K-step 32 (C % 32 == 0)
+  X6_BK32_64,   // gemm_nt_x6_bk32_kernel<128, 64, 3>
+  H3_128,       // gemm_nt_h3_bk32_kernel<128, 128, 3>: fp16x3, K-step 32
+  H3_64,        // gemm_nt_h3_bk32_kernel<128, 64, 4>
+};
+// pis_tune key 10 for a contraction of C channels into N outputs (F(4x4) and F(2x2)); F(6x6) runs
+// the fp16x3 pair whatever the key (64-aligned N, 32-aligned C: wino6_layer)
+WinoGemm choose_wino_gemm(int N, int C);
+inline WinoGemm choose_wino6_gemm(int N) { return N % 128 == 0 ? WinoGemm::H3_128 : WinoGemm::H3_64; }
+
+// the forms of the transform and fused kernels: a function of the tune state alone
+struct WinoVariants {
+  int vw;                    // channels per thread of the F(4x4) input / output transforms, 2 or 4 (key 17)
+  bool out_mask;             // the output transforms' masked form where a mask is given (key 46, vw == 2)
+  bool input_cols, dz_cols;  // single-load-phase input transform / dz passes (key 50)
+  bool dgrad_t;              // format-1 input-gradient filters are the overlap-add form's U' (key 51)
+  bool dgrad_t_xcd;          // ... its output transform in XCD-major block order (key 51 != 2)
+  int fused_g;               // tile groups per block the fused contraction wants (key 15)
+  bool fused_h3;             // the fused contraction runs in fp16x3 (key 22): scales after its filter planes, tile maxima
+  bool fused_stagger;        // ... with staggered wave pairs at 64 channels (key 25)
+  int f6;                    // the F(6x6) transforms: 1 / 2 channels per thread, 3 the two-half form (key 47)
+  bool wgrad_out_v4;         // the float4 weight-gradient output transform (key 48)
+};
+// wino4_gemm_out_x6_kernel<4, 2, kc, g, h3, stg> for kc = 64 or 128 contraction channels over
+// `groups` groups of 32 tiles. The staggered form is G = 4 fp16x3 (128 channels: always, where 4
+// divides the groups; its lockstep form spills); otherwise a wanted G that does not divide the
+// groups falls to G = 1, not to the next smaller one.
+struct FusedForm {
+  int kc, g;
+  bool h3, stg;
+};
+FusedForm wino_fused_form(int kc, int64_t groups, const WinoVariants& v);
+
 // one direction of the layer: the forward (C = Cin, N = Cout) or the input gradient (C = Cout, N = Cin)
 struct ConvDirPlan {
   int C, N;            // contraction channels, outputs
@@ -99,6 +141,7 @@ struct ConvDirPlan {
   ConvAlgo wino;       // the Winograd pipeline it then runs (ALGO_NONE: the shape has none)
   ConvAlgo wino_kept;  // ... with a kept or prepared F(4x4) transform (never F(6x6)); a kept
                        // transform also overrides wino_wanted (resolve_conv3x3)
+  WinoGemm gemm;       // the batched GEMM of wino_kept's pipeline (choose_wino_gemm)
   ConvAlgo fallback;   // small workspace or no policy: halo, generic, or the Cin == 1 kernels
   size_t direct_ws, wino_ws;
   int filter_format;   // pis_conv3x3_filter_format
@@ -108,7 +151,7 @@ struct ConvDirPlan {
 struct Conv3x3Plan {
   int B, H, W, Cin, Cout;
   ConvDirPlan fwd, dgrad;
-  bool fused_h3;      // the fused contraction runs in fp16x3 (key 22): scales after its filter planes, tile maxima
+  WinoVariants wino;  // what the Winograd launchers of either direction and of the weight gradient instantiate
   size_t keep_bytes;  // pis_conv3x3_keep_bytes
   size_t ex_ws;       // pis_conv3x3_ex_ws
   WgradAlgo wgrad;           // with 16-byte aligned operands and the workspace below

@@ -190,11 +190,30 @@ size_t filter_bytes(const Conv3x3Plan& p, const ConvDirPlan& d) {
   switch (d.filter_format) {
     case 1: return nc * sizeof(float);
     case 2:  // fp16x3: hi / lo planes + one scale per output; else the three bf16x6 planes
-      return p.fused_h3 ? 2 * nc * sizeof(_Float16) + (size_t)d.N * sizeof(float) : 3 * nc * sizeof(__bf16);
+      return p.wino.fused_h3 ? 2 * nc * sizeof(_Float16) + (size_t)d.N * sizeof(float) : 3 * nc * sizeof(__bf16);
     case 3: return d.direct_ws;
     case 4: return (size_t)64 * p.Cin * p.Cout * sizeof(float);
     default: return 0;
   }
+}
+
+// the transform and fused-kernel forms (pis_tune keys 15, 17, 22, 25, 46, 47, 48, 50, 51)
+WinoVariants wino_variants() {
+  WinoVariants v{};
+  v.vw = tune_get(PIS_TUNE_WINO_VW) != 4 ? 2 : 4;
+  v.out_mask = tune_get(PIS_TUNE_WINO_OUT_MPF) != 0;
+  const int xf = tune_get(PIS_TUNE_WINO_XFORM), dt = tune_get(PIS_TUNE_WINO_DGRAD_T), go = tune_get(PIS_TUNE_WINO_GEMM_OUT);
+  // key 50: 1 (default) both single-load-phase forms, 0 neither; 2 / 4 the dz passes / the input transform alone
+  v.dz_cols = xf == 1 || (xf & 2) != 0;
+  v.input_cols = xf == 1 || (xf & 4) != 0;
+  v.dgrad_t = dt != 0;
+  v.dgrad_t_xcd = dt != 2;
+  v.fused_g = go == 2 ? 1 : go == 3 ? 2 : go == 4 ? 8 : 4;  // key 15: 1 -> G = 4, 2 -> 1, 3 -> 2, 4 -> 8 (experiments)
+  v.fused_h3 = tune_get(PIS_TUNE_WINO_GEMM_OUT_H3) != 0;
+  v.fused_stagger = tune_get(PIS_TUNE_FUSED_STAGGER) != 0;
+  v.f6 = tune_get(PIS_TUNE_WINO_F6);
+  v.wgrad_out_v4 = tune_get(PIS_TUNE_WGRAD_OUT) == 1;
+  return v;
 }
 
 ConvDirPlan plan_dir(int B, int H, int W, int C, int N, bool is_dgrad, bool wino6) {
@@ -215,6 +234,7 @@ ConvDirPlan plan_dir(int B, int H, int W, int C, int N, bool is_dgrad, bool wino
   else d.wino_kept = ALGO_WINO4_GEMM;
   // F(6x6,3x3): the deep layers' forward and input gradient (no kept or prepared F(4x4) transforms)
   d.wino = (wino6 && d.wino_kept != ALGO_NONE) ? ALGO_WINO6 : d.wino_kept;
+  d.gemm = choose_wino_gemm(N, C);
   d.wino_ws = wino_ws_bytes(m, B, H, W, C, N);
   if (wino6) d.wino_ws = std::max(d.wino_ws, wino6_ws_bytes(B, H, W, C, N));
   if (!is_dgrad && C == 1) d.fallback = (N == 64 && W % 64 == 0) ? ALGO_C1_ROW : ALGO_C1_STREAM;
@@ -255,13 +275,31 @@ WgradKernel choose_wgrad_kernel(const WgradPlan& pl, const WgradOperands& o, con
   return (cols && x6 != 0) ? WgradKernel::X6 : WgradKernel::F32;
 }
 
+WinoGemm choose_wino_gemm(int N, int C) {
+  const int v = tune_get(PIS_TUNE_WINO_TILE);
+  if (v == 1 && N % 256 == 0) return WinoGemm::F32_256;
+  // key 10 >= 3: bf16x6, on the K-step 32 single-buffer kernel where C allows (2-9 % faster,
+  // tools/bench_gemm.py); there key 10 = 4 runs fp16x3 with per-K-step power-of-two tile scales
+  const bool k32 = C % 32 == 0;
+  if (v >= 3 && N % 128 == 0) return !k32 ? WinoGemm::X6_128 : v == 4 ? WinoGemm::H3_128 : WinoGemm::X6_BK32_128;
+  if (v >= 3 && N % 64 == 0) return !k32 ? WinoGemm::X6_64 : v == 4 ? WinoGemm::H3_64 : WinoGemm::X6_BK32_64;
+  if (v == 2 && N % 128 == 0) return WinoGemm::F32_128;
+  if (v == 2 && N % 64 == 0) return WinoGemm::F32_64;
+  return WinoGemm::IGEMM;
+}
+
+FusedForm wino_fused_form(int kc, int64_t groups, const WinoVariants& v) {
+  if (v.fused_h3 && groups % 4 == 0 && (kc == 128 || v.fused_stagger)) return {kc, 4, true, true};
+  return {kc, groups % v.fused_g == 0 ? v.fused_g : 1, v.fused_h3, false};
+}
+
 Conv3x3Plan plan_conv3x3(int B, int H, int W, int Cin, int Cout) {
   Conv3x3Plan p{};
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
   const bool wino6 = wino6_layer(B, H, W, Cin, Cout);
   p.fwd = plan_dir(B, H, W, Cin, Cout, false, wino6);
   p.dgrad = plan_dir(B, H, W, Cout, Cin, true, wino6);
-  p.fused_h3 = tune_get(PIS_TUNE_WINO_GEMM_OUT_H3) != 0;
+  p.wino = wino_variants();
 
   // weight gradient: the direct kernel where its policy takes the forward, else Winograd, halo,
   // the Cin == 1 kernels, generic
@@ -313,8 +351,8 @@ Conv3x3Plan plan_conv3x3(int B, int H, int W, int Cin, int Cout) {
   if (tune_get(PIS_TUNE_WINO_DZ2) != 0 && p.wgrad != WGRAD_DIRECT && p.wino_w.use && p.wino_w.m == 4 && tile4 &&
       p.dgrad.wino_kept != ALGO_NONE && p.dgrad.wino_wanted && !p.dgrad.direct && !wino6)
     p.prep = p.dgrad.wino_kept == ALGO_WINO4_DGRAD_T                  ? PREP_E_ONLY
-             : p.dgrad.wino_kept == ALGO_WINO4_FUSED && p.fused_h3 ? PREP_DZ2_TMAX
-                                                                     : PREP_DZ2;
+             : p.dgrad.wino_kept == ALGO_WINO4_FUSED && p.wino.fused_h3 ? PREP_DZ2_TMAX
+                                                                          : PREP_DZ2;
   return p;
 }
 
@@ -381,4 +419,12 @@ extern "C" int pis_debug_wino_wgrad_plan(int B, int H, int W, int Cin, int Cout,
 
 extern "C" int pis_debug_wino_wgrad_kernel(int B, int H, int W, int Cin, int Cout, int aligned) {
   return pis_debug_wino_wgrad_plan(B, H, W, Cin, Cout, aligned, nullptr, nullptr);
+}
+
+extern "C" int pis_debug_wino_gemm(int N, int C) { return (N > 0 && C > 0) ? (int)choose_wino_gemm(N, C) : -1; }
+
+extern "C" int pis_debug_wino_fused_form(int C, int T) {
+  if ((C != 64 && C != 128) || T <= 0 || T % 32) return -1;
+  const FusedForm f = wino_fused_form(C, T / 32, wino_variants());
+  return f.g | (f.h3 ? 16 : 0) | (f.stg ? 32 : 0);
 }

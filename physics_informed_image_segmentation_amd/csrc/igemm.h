@@ -55,6 +55,9 @@ enum ConvAlgo {
   ALGO_IGEMM,          // generic implicit GEMM
 };
 
+struct Conv3x3Plan;   // conv3x3_plan.h
+struct WinoVariants;  // ... the kernel forms the Winograd launchers below instantiate
+
 // generic implicit GEMM (all tap modes); `batches` independent problems via gridDim.y
 int launch_igemm(const IGemmArgs& a, hipStream_t s, int batches = 1);
 // 3x3 conv (fwd or dgrad-on-flipped-weights) from a staged input halo (W % 16 == 0, H % 8 == 0,
@@ -67,13 +70,14 @@ size_t wino6_ws_bytes(int B, int H, int W, int C, int N);
 // keep_v (optional, F(4x4) only): V is written there instead of the workspace and left for
 // the layer's weight gradient (pis_conv3x3_wgrad_keep)
 // v_ready: V (F(4x4) only) is already in the workspace (pis_conv3x3_bwd_prep)
-int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v = nullptr,
-                   bool v_ready = false);
+// p: the layer's plan (the batched GEMM of a's direction, the transform and fused-kernel forms)
+int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, const Conv3x3Plan& p,
+                   float* keep_v = nullptr, bool v_ready = false);
 float* wino_v_slot(void* ws, int C, int N);
 // one pass over dz: V (input-gradient input transform) and E + bias partials (weight gradient)
 // (tmax != NULL: also the per-tile max |V| the fused fp16x3 dgrad reads, at wino_tmax_slot)
 int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float* V, float* E, float* bpart,
-                    hipStream_t s, float* tmax = nullptr);
+                    hipStream_t s, const WinoVariants& v, float* tmax = nullptr);
 float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N);
 // pis_conv3x3_bwd_prep's record of the V it wrote into ws (checked by the prepared dgrad); e != NULL:
 // the overlap-add form (pis_tune key 51) — no V, the input gradient contracts the weight
@@ -81,18 +85,20 @@ float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N);
 void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tmax, const float* e = nullptr);
 // Winograd weight-gradient pieces for tile edge m (2: F(3x3,2x2), 4: F(3x3,4x4)), nxi = (m+2)^2:
 // V[nxi][T][C] of x, E[nxi][T][N] of dz, dW from M[nxi][N][C]
-int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float* V, hipStream_t s, int m);
+int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float* V, hipStream_t s, int m,
+                      const WinoVariants& v);
 // bpart (m == 4 only, optional, N / 4 must divide 256): per-block channel sums of dz,
 // [wino_dz_blocks()][N], for the bias gradient
 int launch_wino_dz(const float* dz, int ldz, int B, int H, int W, int N, float* E, hipStream_t s, int m,
-                   float* bpart = nullptr);
+                   const WinoVariants& v, float* bpart = nullptr);
 int wino_dz_blocks(int B, int H, int W, int N, int m);
 // the filter operands computed ahead (pis_conv3x3_filter(s)): C contraction channels, N outputs;
 // format as pis_conv3x3_filter_format
 int launch_wino6_filter_only(const float* w, int C, int N, int dgrad, void* out, hipStream_t s);
-int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s);
+int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s,
+                             const WinoVariants& v);
 int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, const int* C, const int* N,
-                              const int* dgrad, const int* format, hipStream_t s);
+                              const int* dgrad, const int* format, hipStream_t s, const WinoVariants& v);
 int wino_dz_blocks_max(int B, int H, int W, int N, int m);  // the largest grid a dz pass of F(m x m) launches (rows of bias partials)
 // M: nsplit split-K slabs sstride floats apart, summed in slab order (nsplit > 1 needs m == 4)
 // The F(3x3,4x4) weight gradient's bias gradient, folded into its output-transform launch:
@@ -108,7 +114,7 @@ struct WgradOutBias {
 constexpr int WINO4_BIAS_XI = 7;
 constexpr float WINO4_BIAS_SCALE = (float)(1.0 / ((double)(1.0f / 3.0f) * (double)(1.0f / 3.0f)));
 int launch_wino_wgrad_out(const float* M, int N, int C, float* dw, int accumulate, hipStream_t s, int m,
-                          int nsplit = 1, int64_t sstride = 0, WgradOutBias bias = WgradOutBias{});
+                          const WinoVariants& v, int nsplit = 1, int64_t sstride = 0, WgradOutBias bias = WgradOutBias{});
 
 // direct 3x3 conv in fp16x3 (direct.hip): shapes it covers (a contraction of C channels into N
 // outputs; the layer's weight gradient), its workspace (split weights), the launch (dgrad_orig: an

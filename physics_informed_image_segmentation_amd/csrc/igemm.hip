@@ -577,8 +577,8 @@ static ConvAlgo resolve(const Conv3x3Plan& p, const IGemmArgs& a, const void* ws
 
 // run the resolved algorithm; keep_v: the layer's kept F(4x4) input transform, which the paths
 // that do not compute it still owe to the weight gradient
-static int launch_conv3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, size_t ws_bytes, hipStream_t s,
-                          float* keep_v = nullptr, bool v_ready = false) {
+static int launch_conv3x3(const Conv3x3Plan& p, ConvAlgo algo, const IGemmArgs& a, int B, void* ws, size_t ws_bytes,
+                          hipStream_t s, float* keep_v = nullptr, bool v_ready = false) {
   int rc = PIS_ERR_ARG;
   switch (algo) {
     case ALGO_NONE: return PIS_ERR_ARG;
@@ -602,13 +602,13 @@ static int launch_conv3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, si
     case ALGO_WINO4_GEMM:
     case ALGO_WINO4_DGRAD_T:
     case ALGO_WINO6:
-    case ALGO_WINO2: return launch_wino3x3(algo, a, B, ws, s, keep_v, v_ready);
+    case ALGO_WINO2: return launch_wino3x3(algo, a, B, ws, s, p, keep_v, v_ready);
     // (PIS_FILTER_READY here: a.wt is the layer's split from pis_conv3x3_filter(s), format 3)
     case ALGO_DIRECT_H3: rc = launch_direct_h3(a, B, ws, ws_bytes, s, a.w_unflipped != 0, a.filter_ready); break;
     case ALGO_HALO: rc = launch_conv3x3_halo(a, s); break;
     case ALGO_IGEMM: rc = launch_igemm(a, s); break;
   }
-  if (!rc && keep_v) rc = launch_wino_input(a.src, a.lds, B, a.H, a.W, a.Csrc, keep_v, s, 4);
+  if (!rc && keep_v) rc = launch_wino_input(a.src, a.lds, B, a.H, a.W, a.Csrc, keep_v, s, 4, p.wino);
   return rc;
 }
 
@@ -656,7 +656,7 @@ extern "C" int pis_conv3x3_fwd_ex(const float* x, int ldx, const float* w_krsc, 
                                                                                  PIS_FILTER_READY));
   a.bias = bias; a.scale = scale;
   const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
-  return launch_conv3x3(resolve(p, a, ws, ws_bytes, false, false), a, B, ws, ws_bytes, (hipStream_t)stream);
+  return launch_conv3x3(p, resolve(p, a, ws, ws_bytes, false, false), a, B, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pis_conv3x3_fwd_keep(const float* x, int ldx, const float* w_krsc, const float* bias,
@@ -672,7 +672,7 @@ extern "C" int pis_conv3x3_fwd_keep(const float* x, int ldx, const float* w_krsc
   IGemmArgs a = conv3x3_args(x, ldx, w_krsc, Cin, Cout, y, ldy, B, H, W, flags & (PIS_RELU | PIS_SCALE | PIS_ACCUMULATE |
                                                                                  PIS_FILTER_READY));
   a.bias = bias; a.scale = scale;
-  return launch_conv3x3(resolve(p, a, ws, ws_bytes, true, false), a, B, ws, ws_bytes, (hipStream_t)stream, keep);
+  return launch_conv3x3(p, resolve(p, a, ws, ws_bytes, true, false), a, B, ws, ws_bytes, (hipStream_t)stream, keep);
 }
 
 extern "C" int pis_conv3x3_fwd_pool(const float* x, int ldx, const float* w_krsc, const float* bias,
@@ -694,7 +694,7 @@ extern "C" int pis_conv3x3_fwd_pool(const float* x, int ldx, const float* w_krsc
   const ConvAlgo algo = resolve(p, a, ws, ws_bytes, keep_v != nullptr, false);
   if (pool_fused(algo)) {
     a.pool = pool;
-    return launch_conv3x3(algo, a, B, ws, ws_bytes, (hipStream_t)stream, keep_v);
+    return launch_conv3x3(p, algo, a, B, ws, ws_bytes, (hipStream_t)stream, keep_v);
   }
   int rc = pis_conv3x3_fwd_keep(x, ldx, w_krsc, bias, scale, y, ldy, B, H, W, Cin, Cout, flags, ws, ws_bytes,
                                 keep, stream);
@@ -723,7 +723,7 @@ extern "C" int pis_conv3x3_filter(const float* w, int B, int H, int W, int Cin, 
     return launch_direct_wsplit_batch(1, &w, &out, &Cin, &Cout, &dg, (hipStream_t)stream);
   // d.C contraction channels into d.N outputs
   if (d.filter_format == 4) return launch_wino6_filter_only(w, d.C, d.N, dg, out, (hipStream_t)stream);
-  return launch_wino4_filter_only(w, d.C, d.N, dg, d.filter_format, out, (hipStream_t)stream);
+  return launch_wino4_filter_only(w, d.C, d.N, dg, d.filter_format, out, (hipStream_t)stream, p.wino);
 }
 
 extern "C" int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream_t stream) {
@@ -736,9 +736,11 @@ extern "C" int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream
   void* dout[PIS_FILTER_MAX_JOBS];
   int dci[PIS_FILTER_MAX_JOBS], dco[PIS_FILTER_MAX_JOBS], ddg[PIS_FILTER_MAX_JOBS];
   int nw = 0, nd = 0;
+  WinoVariants wv{};  // of the tune state: the same in every job's plan
   for (int k = 0; k < n; ++k) {
     const pis_filter_job& j = jobs[k];
     const Conv3x3Plan p = plan_conv3x3(j.B, j.H, j.W, j.Cin, j.Cout);
+    wv = p.wino;
     const ConvDirPlan& d = j.dgrad ? p.dgrad : p.fwd;
     PIS_CHECK_ARG(j.w && j.out && d.filter_format != 0, "pis_conv3x3_filters: a job has no filter transform (no "
                                                         "F(4x4,3x3) GEMM or direct path)");
@@ -753,7 +755,7 @@ extern "C" int pis_conv3x3_filters(const pis_filter_job* jobs, int n, pis_stream
     N[nw] = d.N;  // output channels
     ++nw;
   }
-  int rc = nw ? launch_wino4_filter_batch(nw, w, out, C, N, dg, fmt, (hipStream_t)stream) : PIS_OK;
+  int rc = nw ? launch_wino4_filter_batch(nw, w, out, C, N, dg, fmt, (hipStream_t)stream, wv) : PIS_OK;
   if (!rc && nd) rc = launch_direct_wsplit_batch(nd, dw, dout, dci, dco, ddg, (hipStream_t)stream);
   return rc;
 }
@@ -780,8 +782,8 @@ extern "C" int pis_conv3x3_dgrad_ex(const float* dz, int ldz, const float* w_fli
   a.is_dgrad = 1;
   const bool prepared = (flags & PIS_WINO_PREPARED) != 0;
   const Conv3x3Plan p = plan_conv3x3(B, H, W, Cin, Cout);
-  return launch_conv3x3(resolve(p, a, ws, ws_bytes, false, prepared), a, B, ws, ws_bytes, (hipStream_t)stream, nullptr,
-                        prepared);
+  return launch_conv3x3(p, resolve(p, a, ws, ws_bytes, false, prepared), a, B, ws, ws_bytes, (hipStream_t)stream,
+                        nullptr, prepared);
 }
 
 extern "C" int pis_convt2x2_fwd(const float* x, int ldx, const float* w_ijoc, const float* bias,

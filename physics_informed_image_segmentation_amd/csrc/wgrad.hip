@@ -1703,8 +1703,8 @@ __global__ __launch_bounds__(256) void wgrad_c1_row_kernel(const float* __restri
 }
 
 static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* dw, float* db, int B, int H, int W,
-                      int Cin, int Cout, int acc, const WinoWgradPlan& p, void* ws, hipStream_t s,
-                      const float* keep_v = nullptr, bool e_ready = false) {
+                      int Cin, int Cout, int acc, const WinoWgradPlan& p, const WinoVariants& wv, void* ws,
+                      hipStream_t s, const float* keep_v = nullptr, bool e_ready = false) {
   char* base = (char*)ws;
   float* V = (float*)base;
   float* E = (float*)(base + p.off_E);
@@ -1712,8 +1712,8 @@ static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* 
   float* M = (float*)(base + p.off_M);
   int rc = 0;
   if (keep_v && p.m == 4) V = const_cast<float*>(keep_v);  // the forward's transform of x
-  else rc = launch_wino_input(x, ldx, B, H, W, Cin, V, s, p.m);
-  if (!rc && !e_ready) rc = launch_wino_dz(dz, ldz, B, H, W, Cout, E, s, p.m, nullptr);
+  else rc = launch_wino_input(x, ldx, B, H, W, Cin, V, s, p.m, wv);
+  if (!rc && !e_ready) rc = launch_wino_dz(dz, ldz, B, H, W, Cout, E, s, p.m, wv);
   if (rc) return rc;
   float* gbias = (db && p.gemm_bias) ? (float*)(base + p.off_cs) : nullptr;
   WgradArgs a{};
@@ -1736,10 +1736,10 @@ static int wino_wgrad(const float* x, int ldx, const float* dz, int ldz, float* 
   // keep the parallel slab reduction
   const WgradOutBias bf{gbias, gbias ? gp.splits : 0, db, WINO4_BIAS_SCALE};
   if (p.m == 4 && gp.splits <= 16) {
-    if (!rc) rc = launch_wino_wgrad_out(part, Cout, Cin, dw, acc, s, p.m, gp.splits, a.split_stride, bf);
+    if (!rc) rc = launch_wino_wgrad_out(part, Cout, Cin, dw, acc, s, p.m, wv, gp.splits, a.split_stride, bf);
   } else {
     if (!rc) rc = reduce_slabs_pitched(part, gp.splits, a.split_stride, a.split_stride, M, 0, s);
-    if (!rc) rc = launch_wino_wgrad_out(M, Cout, Cin, dw, acc, s, p.m, 1, 0, bf);
+    if (!rc) rc = launch_wino_wgrad_out(M, Cout, Cin, dw, acc, s, p.m, wv, 1, 0, bf);
   }
   if (!rc && db && !gbias) rc = colsum(dz, ldz, (int64_t)B * H * W, Cout, db, acc, base + p.off_cs, p.total - p.off_cs, s);
   return rc;
@@ -1771,7 +1771,7 @@ extern "C" int pis_conv3x3_wgrad_keep(const float* x, int ldx, const float* dz, 
     return pis_conv3x3_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, flags, ws, ws_bytes, stream);
   PIS_CHECK_ARG(x && dz && dw_krsc && ldz % 4 == 0, "pis_conv3x3_wgrad_keep: bad arguments");
   PIS_CHECK_ARG(ws && ws_bytes >= wp.total, "pis_conv3x3_wgrad_keep: workspace too small");
-  return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, flags & PIS_ACCUMULATE, wp, ws,
+  return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, flags & PIS_ACCUMULATE, wp, p.wino, ws,
                     (hipStream_t)stream, keep, prepared);
 }
 
@@ -1791,13 +1791,13 @@ extern "C" int pis_conv3x3_bwd_prep(const float* dz, int ldz, int B, int H, int 
     // the overlap-add input gradient (pis_tune key 51) contracts E too: one set of planes, written
     // once, read by both calls in place. pis_conv3x3_wgrad_keep with PIS_WINO_PREPARED only reads
     // [off_E, off_part) (it writes the split slabs, M and the bias partials behind it).
-    const int rc = launch_wino_dz(dz, ldz, B, H, W, Cout, E, (hipStream_t)stream, 4, nullptr);
+    const int rc = launch_wino_dz(dz, ldz, B, H, W, Cout, E, (hipStream_t)stream, 4, p.wino);
     if (!rc) wino_prep_record(ws_dgrad, B, H, W, Cout, Cin, false, E);
     return rc ? rc : 1;
   }
   float* tmax = p.prep == PREP_DZ2_TMAX ? wino_tmax_slot(ws_dgrad, B, H, W, Cout, Cin) : nullptr;
   // (no bias partials: the weight gradient's GEMM sums them from E, WinoWgradPlan gemm_bias)
-  const int rc = launch_wino_dz2(dz, ldz, B, H, W, Cout, V, E, nullptr, (hipStream_t)stream, tmax);
+  const int rc = launch_wino_dz2(dz, ldz, B, H, W, Cout, V, E, nullptr, (hipStream_t)stream, p.wino, tmax);
   // the dgrad_ex that consumes this V checks that it decides the same tile-maxima format
   if (!rc) wino_prep_record(ws_dgrad, B, H, W, Cout, Cin, tmax != nullptr);
   return rc ? rc : 1;
@@ -1821,7 +1821,7 @@ extern "C" int pis_conv3x3_wgrad(const float* x, int ldx, const float* dz, int l
   if (algo == WGRAD_DIRECT)
     return launch_direct_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, ws, ws_bytes, s);
   if (algo == WGRAD_WINO4 || algo == WGRAD_WINO2)
-    return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, p.wino_w, ws, s);
+    return wino_wgrad(x, ldx, dz, ldz, dw_krsc, db, B, H, W, Cin, Cout, acc, p.wino_w, p.wino, ws, s);
   if (algo == WGRAD_HALO) {
     const HaloPlan& hp = p.halo_w;
     W3Args a{};

@@ -19,7 +19,7 @@
 //   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
 //   G   = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
 //   A^T = [1 1 1 0; 0 1 -1 -1]
-#include "igemm.h"
+#include "conv3x3_plan.h"
 
 namespace pis {
 
@@ -2486,54 +2486,36 @@ static int grid_of(int64_t work) { return (int)std::max<int64_t>(1, std::min<int
 
 // the F(4x4,3x3) output transform, 2 (default) or 4 channels per thread (pis_tune key 17;
 // tools/bench_kernels.py --key 17: 2 channels halve the registers, +2-11 % on the 512^2-256^2 layers)
-static void launch_wino4_output(const float* Mt, const IGemmArgs& a, int B, int64_t T, int N, hipStream_t s) {
-  if (tune_get(PIS_TUNE_WINO_VW) != 4)
-    if ((a.flags & PIS_MASK) && a.mask && tune_get(PIS_TUNE_WINO_OUT_MPF) != 0)
-      hipLaunchKernelGGL((wino4_output_kernel<2, true>), dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B);
-    else
-      hipLaunchKernelGGL(wino4_output_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B);
-  else
-    hipLaunchKernelGGL(wino4_output_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B);
+static void launch_wino4_output(const float* Mt, const IGemmArgs& a, int B, int64_t T, int N, hipStream_t s,
+                                const WinoVariants& v) {
+  const bool masked = (a.flags & PIS_MASK) && a.mask && v.out_mask;
+  void (*fn)(const float*, IGemmArgs, int) =
+      v.vw == 4 ? wino4_output_kernel<4> : masked ? wino4_output_kernel<2, true> : wino4_output_kernel<2>;
+  hipLaunchKernelGGL(fn, dim3(grid_of(T * (N / v.vw))), dim3(256), 0, s, Mt, a, B);
 }
 
 // the overlap-add output transform of an input gradient whose contraction ran on E (pis_tune key 51)
 // (key 51 = 2: without the XCD-major block order, its A/B)
-static void launch_wino4_output_t(const float* Mt, const IGemmArgs& a, int B, int64_t T, int N, hipStream_t s) {
-  const int xcd = tune_get(PIS_TUNE_WINO_DGRAD_T) != 2;
-  if (tune_get(PIS_TUNE_WINO_VW) != 4)
-    if ((a.flags & PIS_MASK) && a.mask && tune_get(PIS_TUNE_WINO_OUT_MPF) != 0)
-      hipLaunchKernelGGL((wino4_output_t_kernel<2, true>), dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B, xcd);
-    else
-      hipLaunchKernelGGL(wino4_output_t_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B, xcd);
-  else
-    hipLaunchKernelGGL(wino4_output_t_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B, xcd);
-}
-
-// which of the F(4x4) input-side transforms take their single-load-phase form (pis_tune key 50):
-// 1 (default) both, 0 neither; 2 / 4 the merged dz pass / the input transform alone
-enum { XF_DZ2 = 2, XF_INPUT = 4 };
-static bool wino_xform(int part) {
-  const int v = tune_get(PIS_TUNE_WINO_XFORM);
-  return v == 1 || (v & part) != 0;
+static void launch_wino4_output_t(const float* Mt, const IGemmArgs& a, int B, int64_t T, int N, hipStream_t s,
+                                  const WinoVariants& v) {
+  const bool masked = (a.flags & PIS_MASK) && a.mask && v.out_mask;
+  void (*fn)(const float*, IGemmArgs, int, int) =
+      v.vw == 4 ? wino4_output_t_kernel<4> : masked ? wino4_output_t_kernel<2, true> : wino4_output_t_kernel<2>;
+  hipLaunchKernelGGL(fn, dim3(grid_of(T * (N / v.vw))), dim3(256), 0, s, Mt, a, B, v.dgrad_t_xcd ? 1 : 0);
 }
 
 // the F(4x4,3x3) input transform, 2 (default) or 4 channels per thread (pis_tune key 17)
 // tmax (C % 64 == 0): also the per-tile, per-64-channel-chunk max |V| (the fp16x3 tile scales)
-static void launch_wino4_input(int64_t T, int C, hipStream_t s, const float* x, int ldx, int B, int H, int W, int,
-                               float* V, float* tmax = nullptr) {
-  const bool vw2 = tune_get(PIS_TUNE_WINO_VW) != 4, cols = wino_xform(XF_INPUT);
-  const dim3 grid(grid_of(T * (C / (vw2 ? 2 : 4))));
-#define PIS_INPUT_LAUNCH(VW, TM)                                                                                  \
-  do {                                                                                                            \
-    if (cols) hipLaunchKernelGGL((wino4_input_cols_kernel<VW, TM>), grid, dim3(256), 0, s, x, ldx, B, H, W, C, V, \
-                                 tmax);                                                                           \
-    else hipLaunchKernelGGL((wino4_input_kernel<VW, TM>), grid, dim3(256), 0, s, x, ldx, B, H, W, C, V, tmax);    \
-  } while (0)
-  if (tmax && vw2) PIS_INPUT_LAUNCH(2, true);
-  else if (tmax) PIS_INPUT_LAUNCH(4, true);
-  else if (vw2) PIS_INPUT_LAUNCH(2, false);
-  else PIS_INPUT_LAUNCH(4, false);
-#undef PIS_INPUT_LAUNCH
+static void launch_wino4_input(int64_t T, int C, hipStream_t s, const float* x, int ldx, int B, int H, int W,
+                               float* V, const WinoVariants& v, float* tmax = nullptr) {
+  // [single-load-phase form][tile maxima][4 channels per thread]
+  static void (*const fn[2][2][2])(const float*, int, int, int, int, int, float*, float*) = {
+      {{wino4_input_kernel<2, false>, wino4_input_kernel<4, false>},
+       {wino4_input_kernel<2, true>, wino4_input_kernel<4, true>}},
+      {{wino4_input_cols_kernel<2, false>, wino4_input_cols_kernel<4, false>},
+       {wino4_input_cols_kernel<2, true>, wino4_input_cols_kernel<4, true>}}};
+  hipLaunchKernelGGL(fn[v.input_cols][tmax != nullptr][v.vw == 4], dim3(grid_of(T * (C / v.vw))), dim3(256), 0, s, x,
+                     ldx, B, H, W, C, V, tmax);
 }
 
 // the F(4x4,3x3) filter transform of a's weights (the tiled kernel for unflipped 32-aligned shapes)
@@ -2553,71 +2535,62 @@ static void launch_wino4_filter(const IGemmArgs& a, int N, int C, float* U, int 
                        transposed, Up, gt);
 }
 
-// the fused 64 -> 64 kernel's arithmetic (pis_tune key 22): fp16x3 planes instead of bf16x6
-static bool wino_gemm_out_h3() { return tune_get(PIS_TUNE_WINO_GEMM_OUT_H3) != 0; }
-
+// the fused contraction + output transform, in the form the planner names (wino_fused_form). 8 waves:
+// 32 tiles x 64 channels per block, G such groups per block; a.N / 64 blocks per group (pis_tune
+// key 26: N = 128 too). tmax: the fp16x3 forms' tile maxima
 static int launch_wino_gemm_out(const float* V, const __bf16* Up, const IGemmArgs& a, int B, int64_t T,
-                                hipStream_t s, const float* tmax) {
-  // 8 waves: 32 tiles x 64 channels per block; G such groups per block where they divide
-  // (pis_tune key 15: 1 -> G = 4, 2 -> 1, 3 -> 2, 4 -> 8: experiments)
+                                hipStream_t s, const WinoVariants& v, const float* tmax) {
+  // [128 channels][fp16x3][G = 1, 2, 4, 8 in lockstep; G = 4 staggered]
+  static void (*const fn[2][2][5])(const float*, const __bf16*, IGemmArgs, int, const float*) = {
+      {{wino4_gemm_out_x6_kernel<4, 2, 64, 1>, wino4_gemm_out_x6_kernel<4, 2, 64, 2>,
+        wino4_gemm_out_x6_kernel<4, 2, 64, 4>, wino4_gemm_out_x6_kernel<4, 2, 64, 8>, nullptr},
+       {wino4_gemm_out_x6_kernel<4, 2, 64, 1, true>, wino4_gemm_out_x6_kernel<4, 2, 64, 2, true>,
+        wino4_gemm_out_x6_kernel<4, 2, 64, 4, true>, wino4_gemm_out_x6_kernel<4, 2, 64, 8, true>,
+        wino4_gemm_out_x6_kernel<4, 2, 64, 4, true, true>}},
+      {{wino4_gemm_out_x6_kernel<4, 2, 128, 1>, wino4_gemm_out_x6_kernel<4, 2, 128, 2>,
+        wino4_gemm_out_x6_kernel<4, 2, 128, 4>, wino4_gemm_out_x6_kernel<4, 2, 128, 8>, nullptr},
+       {wino4_gemm_out_x6_kernel<4, 2, 128, 1, true>, wino4_gemm_out_x6_kernel<4, 2, 128, 2, true>,
+        wino4_gemm_out_x6_kernel<4, 2, 128, 4, true>, wino4_gemm_out_x6_kernel<4, 2, 128, 8, true>,
+        wino4_gemm_out_x6_kernel<4, 2, 128, 4, true, true>}}};
   const int64_t groups = T / 32;
-  const int nblk = a.N / 64;  // 64-channel slices (pis_tune key 26: N = 128 too)
-  const int mode = tune_get(PIS_TUNE_WINO_GEMM_OUT);
-  const int G = mode == 2 ? 1 : mode == 3 ? 2 : mode == 4 ? 8 : 4;
-  const dim3 blk(512);
-  if (a.Csrc == 128) {
-    // KC = 128 always staggered where it can be: that form fits 250 VGPRs, the lockstep one spills
-    if (wino_gemm_out_h3() && groups % 4 == 0) {
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 4, true, true>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up,
-                         a, B, tmax);
-    } else if (wino_gemm_out_h3()) {
-      if (G == 8 && groups % 8 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 8, true>), dim3((int)(groups / 8) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else if (G == 4 && groups % 4 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 4, true>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else if (G == 2 && groups % 2 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 2, true>), dim3((int)(groups / 2) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 1, true>), dim3((int)groups * nblk), blk, 0, s, V, Up, a, B, tmax);
-    } else if (G == 8 && groups % 8 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 8>), dim3((int)(groups / 8) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else if (G == 4 && groups % 4 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 4>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else if (G == 2 && groups % 2 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 2>), dim3((int)(groups / 2) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 128, 1>), dim3((int)groups * nblk), blk, 0, s, V, Up, a, B, nullptr);
-  } else {
-  if (wino_gemm_out_h3() && tune_get(PIS_TUNE_FUSED_STAGGER) != 0 && groups % 4 == 0) {
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 4, true, true>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up,
-                         a, B, tmax);
-    } else if (wino_gemm_out_h3()) {
-      if (G == 8 && groups % 8 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 8, true>), dim3((int)(groups / 8) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else if (G == 4 && groups % 4 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 4, true>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else if (G == 2 && groups % 2 == 0)
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 2, true>), dim3((int)(groups / 2) * nblk), blk, 0, s, V, Up, a,
-                           B, tmax);
-      else
-        hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 1, true>), dim3((int)groups * nblk), blk, 0, s, V, Up, a, B, tmax);
-    } else if (G == 8 && groups % 8 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 8>), dim3((int)(groups / 8) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else if (G == 4 && groups % 4 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 4>), dim3((int)(groups / 4) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else if (G == 2 && groups % 2 == 0)
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 2>), dim3((int)(groups / 2) * nblk), blk, 0, s, V, Up, a, B, nullptr);
-    else
-      hipLaunchKernelGGL((wino4_gemm_out_x6_kernel<4, 2, 64, 1>), dim3((int)groups * nblk), blk, 0, s, V, Up, a, B, nullptr);
-  }
+  const FusedForm f = wino_fused_form(a.Csrc, groups, v);
+  hipLaunchKernelGGL(fn[f.kc == 128][f.h3][f.stg ? 4 : f.g == 8 ? 3 : f.g / 2], dim3((int)(groups / f.g) * (a.N / 64)),
+                     dim3(512), 0, s, V, Up, a, B, tmax);
   return launch_status("wino_gemm_out");
 }
 
+// the batched NT GEMM the planner chose (conv3x3_plan.h): Mt[xi] (T x N) = V[xi] (T x C) . U[xi]^T
+// (N x C) for xi < nxi, on 128 x BN tiles
+static int launch_wino_gemm(WinoGemm g, const float* V, const float* U, float* Mt, int64_t T, int N, int C, int nxi,
+                            hipStream_t s, const char* what = "wino_gemm") {
+  static const struct {
+    void (*fn)(const float*, const float*, float*, int, int, int, int64_t, int64_t, int64_t);
+    int bn;
+  } tab[] = {  // in WinoGemm's order
+      {nullptr, 0},
+      {gemm_nt_kernel<128, 256>, 256},
+      {gemm_nt_kernel<128, 128>, 128},
+      {gemm_nt_kernel<128, 64>, 64},
+      {gemm_nt_x6_kernel<128, 128>, 128},
+      {gemm_nt_x6_kernel<128, 64>, 64},
+      {gemm_nt_x6_bk32_kernel<128, 128, 3>, 128},
+      {gemm_nt_x6_bk32_kernel<128, 64, 3>, 64},
+      {gemm_nt_h3_bk32_kernel<128, 128, 3>, 128},
+      {gemm_nt_h3_bk32_kernel<128, 64, 4>, 64},
+  };
+  if (g == WinoGemm::IGEMM) {
+    IGemmArgs gm{};
+    gm.src = V; gm.lds = C; gm.Hs = 1; gm.Ws = (int)T; gm.H = 1; gm.W = (int)T; gm.M = (int)T;
+    gm.Csrc = C; gm.ntaps = 1; gm.tap_mode = TAP_ONE; gm.wt = U; gm.ldw = C; gm.N = N;
+    gm.epi = EPI_NHWC; gm.dst = Mt; gm.ldd = N; gm.flags = 0;
+    gm.bs_src = T * C; gm.bs_wt = (int64_t)N * C; gm.bs_dst = T * N;
+    return launch_igemm(gm, s, nxi);
+  }
+  const auto& k = tab[(int)g];
+  hipLaunchKernelGGL(k.fn, dim3((int)cdiv(T, 128) * (N / k.bn), nxi), dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
+                     (int64_t)N * C, T * N);
+  return launch_status(what);
+}
 
 static int64_t wino6_tiles(int B, int H, int W) { return (int64_t)B * ((H + 5) / 6) * ((W + 5) / 6); }
 
@@ -2643,7 +2616,7 @@ int launch_wino6_filter_only(const float* w, int C, int N, int dgrad, void* out,
 
 // one F(6x6,3x3) convolution (a: as launch_wino3x3): filter transform (or a.wt ready: U[64][N][C]),
 // input transform, the 64 batched fp16x3 GEMMs, output transform + epilogue
-static int launch_wino6(const IGemmArgs& a, int B, void* ws, hipStream_t s) {
+static int launch_wino6(const IGemmArgs& a, int B, void* ws, hipStream_t s, const WinoVariants& v) {
   const int C = a.Csrc, N = a.N;
   const int64_t T = wino6_tiles(B, a.H, a.W);
   float* U = (float*)ws;
@@ -2653,38 +2626,23 @@ static int launch_wino6(const IGemmArgs& a, int B, void* ws, hipStream_t s) {
     return set_error("launch_wino6: unflipped weights need 32-aligned channels"), PIS_ERR_ARG;
   if (a.filter_ready) U = const_cast<float*>(a.wt);
   else launch_wino6_filter(a.wt, a.ldw, N, C, a.w_unflipped ? 1 : 0, U, s);
-  // channels per thread of the transforms (key 47: 1 -> 1, 2 -> 2): the 64-value tiles hold 64 VW
-  // accumulators per thread
-  const int f6 = tune_get(PIS_TUNE_WINO_F6);
-  const bool vw2 = f6 == 2;
-  if (f6 == 3)
-    hipLaunchKernelGGL(wino6_input2h_kernel, dim3(grid_of(T * (C / 2))), dim3(256), 0, s, a.src, a.lds, B, a.H, a.W,
-                       C, V);
-  else if (vw2)
-    hipLaunchKernelGGL(wino6_input_kernel<2>, dim3(grid_of(T * (C / 2))), dim3(256), 0, s, a.src, a.lds, B, a.H, a.W,
-                       C, V);
-  else
-    hipLaunchKernelGGL(wino6_input_kernel<1>, dim3(grid_of(T * C)), dim3(256), 0, s, a.src, a.lds, B, a.H, a.W, C, V);
+  // channels per thread of the transforms (key 47: 1 -> 1, 2 and 3 -> 2; 3: the two-half forms): the
+  // 64-value tiles hold 64 VW accumulators per thread
+  const int vw = v.f6 == 2 || v.f6 == 3 ? 2 : 1;
+  void (*in)(const float*, int, int, int, int, int, float*) =
+      v.f6 == 3 ? wino6_input2h_kernel : vw == 2 ? wino6_input_kernel<2> : wino6_input_kernel<1>;
+  hipLaunchKernelGGL(in, dim3(grid_of(T * (C / vw))), dim3(256), 0, s, a.src, a.lds, B, a.H, a.W, C, V);
   int rc = launch_status("wino6_transforms");
   if (rc) return rc;
   const double flop = 2.0 * 64 * (double)T * N * C;
   launch_hook("wino_gemm", 0, s, flop);
-  if (N % 128 == 0) {
-    const dim3 grid((int)cdiv(T, 128) * (N / 128), 64);
-    hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                       (int64_t)N * C, T * N);
-  } else {
-    const dim3 grid((int)cdiv(T, 128) * (N / 64), 64);
-    hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 64, 4>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                       (int64_t)N * C, T * N);
-  }
+  rc = launch_wino_gemm(choose_wino6_gemm(N), V, U, Mt, T, N, C, 64, s, "wino6_gemm");
   launch_hook("wino_gemm", 1, s, flop);
-  rc = launch_status("wino6_gemm");
   if (rc) return rc;
   gemm_done(s);
-  if (f6 == 3) hipLaunchKernelGGL((wino6_output_kernel<2, true>), dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B);
-  else if (vw2) hipLaunchKernelGGL(wino6_output_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, Mt, a, B);
-  else hipLaunchKernelGGL(wino6_output_kernel<1>, dim3(grid_of(T * N)), dim3(256), 0, s, Mt, a, B);
+  void (*out)(const float*, IGemmArgs, int) =
+      v.f6 == 3 ? wino6_output_kernel<2, true> : vw == 2 ? wino6_output_kernel<2> : wino6_output_kernel<1>;
+  hipLaunchKernelGGL(out, dim3(grid_of(T * (N / vw))), dim3(256), 0, s, Mt, a, B);
   return launch_status("wino6_output");
 }
 
@@ -2699,13 +2657,16 @@ size_t wino_ws_bytes(int m, int B, int H, int W, int C, int N) {
   return (size_t)(nxi * ((int64_t)N * C + T * C + T * N) + extra) * sizeof(float) + 1024;
 }
 
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, const float** e);
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, bool fused_h3,
+                           const float** e);
 
 // a describes the direct conv (src/lds = input, wt/ldw = KRSC weights, N outputs, epilogue); algo:
 // the pipeline to run, as conv3x3_plan.h resolved it for this call (even H and W, 4-aligned
-// channels and strides; F(4x4) / F(6x6): H, W % 4 == 0)
-int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, float* keep_v, bool v_ready) {
+// channels and strides; F(4x4) / F(6x6): H, W % 4 == 0); p: the plan it was resolved from
+int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream_t s, const Conv3x3Plan& p,
+                   float* keep_v, bool v_ready) {
   const int C = a.Csrc, N = a.N;
+  const WinoVariants& v = p.wino;
   const int m = algo == ALGO_WINO2 ? 2 : 4, nxi = (m + 2) * (m + 2);
   if (a.H % m || a.W % m || C % 4 || N % 4 || a.lds % 4 || a.ldd % 4 ||
       !(algo == ALGO_WINO2 || algo == ALGO_WINO4_GEMM || algo == ALGO_WINO4_FUSED || algo == ALGO_WINO6 ||
@@ -2721,11 +2682,11 @@ int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream
   if (keep_v && m == 4) V = keep_v;
   const float* e_prep = nullptr;  // a prepared overlap-add input gradient's E (in the weight gradient's workspace)
   if (v_ready && m == 4) {
-    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N, algo, &e_prep);
+    const int rc = wino_prep_check(ws, B, a.H, a.W, C, N, algo, v.fused_h3, &e_prep);
     if (rc) return rc;
   }
   // F(6x6,3x3): the deep layers' forward and input gradient (no kept or prepared F(4x4) transforms)
-  if (algo == ALGO_WINO6) return launch_wino6(a, B, ws, s);
+  if (algo == ALGO_WINO6) return launch_wino6(a, B, ws, s, v);
   const double flop = 2.0 * nxi * (double)T * N * C;
   if (a.filter_ready && m != 4)
     return set_error("launch_wino3x3: PIS_FILTER_READY needs the F(4x4,3x3) GEMM path"), PIS_ERR_ARG;
@@ -2733,15 +2694,13 @@ int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream
     // the pre-split filter planes (1.5x U's bytes) go where M would have been
     __bf16* Up = reinterpret_cast<__bf16*>(Mt);
     if (a.filter_ready) Up = const_cast<__bf16*>(reinterpret_cast<const __bf16*>(a.wt));
-    else launch_wino4_filter(a, N, C, U, 0, Up, s, wino_gemm_out_h3());
-    float* tmax = wino_gemm_out_h3() ? wino_tmax_slot(ws, B, a.H, a.W, C, N) : nullptr;
-    if (!v_ready)
-      launch_wino4_input(T, C, s, a.src, a.lds, B, a.H, a.W,
-                         C, V, tmax);
+    else launch_wino4_filter(a, N, C, U, 0, Up, s, v.fused_h3);
+    float* tmax = v.fused_h3 ? wino_tmax_slot(ws, B, a.H, a.W, C, N) : nullptr;
+    if (!v_ready) launch_wino4_input(T, C, s, a.src, a.lds, B, a.H, a.W, V, v, tmax);
     int rc = launch_status("wino_transforms");
     if (rc) return rc;
     launch_hook("wino_gemm_out", 0, s, flop);
-    rc = launch_wino_gemm_out(V, Up, a, B, T, s, tmax);
+    rc = launch_wino_gemm_out(V, Up, a, B, T, s, v, tmax);
     launch_hook("wino_gemm_out", 1, s, flop);
     gemm_done(s);
     return rc;
@@ -2756,11 +2715,11 @@ int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream
     if (a.filter_ready) U = const_cast<float*>(a.wt);
     else launch_wino4_filter(a, N, C, U, 0, nullptr, s, false, 1);
     if (v_ready) V = const_cast<float*>(e_prep);
-    else if (const int rc = launch_wino_dz(a.src, a.lds, B, a.H, a.W, C, V, s, 4, nullptr)) return rc;
+    else if (const int rc = launch_wino_dz(a.src, a.lds, B, a.H, a.W, C, V, s, 4, v)) return rc;
   } else if (m == 4) {
     if (a.filter_ready) U = const_cast<float*>(a.wt);
     else launch_wino4_filter(a, N, C, U, 0, nullptr, s);
-    if (!v_ready) launch_wino4_input(T, C, s, a.src, a.lds, B, a.H, a.W, C, V, nullptr);
+    if (!v_ready) launch_wino4_input(T, C, s, a.src, a.lds, B, a.H, a.W, V, v);
   } else {
     hipLaunchKernelGGL(wino_filter_kernel, dim3(grid_of((int64_t)N * C)), dim3(256), 0, s, a.wt, a.ldw, N, C, U);
     hipLaunchKernelGGL(wino_input_kernel, dim3(grid_of(T * (C / 4))), dim3(256), 0, s, a.src, a.lds, B, a.H, a.W,
@@ -2768,91 +2727,37 @@ int launch_wino3x3(ConvAlgo algo, const IGemmArgs& a, int B, void* ws, hipStream
   }
   int rc = launch_status("wino_transforms");
   if (rc) return rc;
-    launch_hook("wino_gemm", 0, s, flop);
-  const int v = tune_get(PIS_TUNE_WINO_TILE);
-  if (v == 1 && N % 256 == 0) {
-    const dim3 grid((int)cdiv(T, 128) * (N / 256), nxi);
-    hipLaunchKernelGGL((gemm_nt_kernel<128, 256>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                       (int64_t)N * C, T * N);
-    rc = launch_status("wino_gemm");
-  } else if (v == 4 && N % 64 == 0 && C % 32 == 0) {
-    // fp16x3 with per-K-step power-of-two tile scales (gemm_nt_h3_bk32_kernel)
-    if (N % 128 == 0) {
-      const dim3 grid((int)cdiv(T, 128) * (N / 128), nxi);
-      hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C,
-                         T * C, (int64_t)N * C, T * N);
-    } else {
-      const dim3 grid((int)cdiv(T, 128) * (N / 64), nxi);
-      hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 64, 4>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C,
-                         T * C, (int64_t)N * C, T * N);
-    }
-    rc = launch_status("wino_gemm");
-  } else if (v >= 3 && N % 128 == 0) {
-    // K-step 32 single-buffer variant where C allows: 2-9 % faster (tools/bench_gemm.py)
-    const dim3 grid((int)cdiv(T, 128) * (N / 128), nxi);
-    if (C % 32 == 0)
-      hipLaunchKernelGGL((gemm_nt_x6_bk32_kernel<128, 128, 3>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C,
-                         T * C, (int64_t)N * C, T * N);
-    else
-      hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 128>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                         (int64_t)N * C, T * N);
-    rc = launch_status("wino_gemm");
-  } else if (v >= 3 && N % 64 == 0) {
-    const dim3 grid((int)cdiv(T, 128) * (N / 64), nxi);
-    if (C % 32 == 0)
-      hipLaunchKernelGGL((gemm_nt_x6_bk32_kernel<128, 64, 3>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C,
-                         T * C, (int64_t)N * C, T * N);
-    else
-      hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 64>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                         (int64_t)N * C, T * N);
-    rc = launch_status("wino_gemm");
-  } else if (v == 2 && N % 128 == 0) {
-    const dim3 grid((int)cdiv(T, 128) * (N / 128), nxi);
-    hipLaunchKernelGGL((gemm_nt_kernel<128, 128>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                       (int64_t)N * C, T * N);
-    rc = launch_status("wino_gemm");
-  } else if (v == 2 && N % 64 == 0) {
-    const dim3 grid((int)cdiv(T, 128) * (N / 64), nxi);
-    hipLaunchKernelGGL((gemm_nt_kernel<128, 64>), grid, dim3(256), 0, s, V, U, Mt, (int)T, N, C, T * C,
-                       (int64_t)N * C, T * N);
-    rc = launch_status("wino_gemm");
-  } else {
-    IGemmArgs gm{};
-    gm.src = V; gm.lds = C; gm.Hs = 1; gm.Ws = (int)T; gm.H = 1; gm.W = (int)T; gm.M = (int)T;
-    gm.Csrc = C; gm.ntaps = 1; gm.tap_mode = TAP_ONE; gm.wt = U; gm.ldw = C; gm.N = N;
-    gm.epi = EPI_NHWC; gm.dst = Mt; gm.ldd = N; gm.flags = 0;
-    gm.bs_src = T * C; gm.bs_wt = (int64_t)N * C; gm.bs_dst = T * N;
-    rc = launch_igemm(gm, s, nxi);
-  }
+  launch_hook("wino_gemm", 0, s, flop);
+  rc = launch_wino_gemm((a.is_dgrad ? p.dgrad : p.fwd).gemm, V, U, Mt, T, N, C, nxi, s);
   launch_hook("wino_gemm", 1, s, flop);
   if (rc) return rc;
   gemm_done(s);
   if (dgrad_t)
-    launch_wino4_output_t(Mt, a, B, T, N, s);
+    launch_wino4_output_t(Mt, a, B, T, N, s, v);
   else if (m == 4)
-    launch_wino4_output(Mt, a, B, T, N, s);
+    launch_wino4_output(Mt, a, B, T, N, s, v);
   else
     hipLaunchKernelGGL(wino_output_kernel, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, Mt, a, B);
   return launch_status("wino_output");
 }
 
-int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s) {
+int launch_wino4_filter_only(const float* w, int C, int N, int dgrad, int format, void* out, hipStream_t s,
+                             const WinoVariants& v) {
   IGemmArgs a{};
   a.wt = w; a.ldw = 9 * C; a.w_unflipped = dgrad;
   if (dgrad && (N % 32 || C % 32)) return set_error("pis_conv3x3_filter: the input-gradient transform needs "
                                                     "32-aligned channels"), PIS_ERR_ARG;
-  if (format == 2 && wino_gemm_out_h3() && (C % 64 || N % 4))
+  if (format == 2 && v.fused_h3 && (C % 64 || N % 4))
     return set_error("pis_conv3x3_filter: fp16x3 planes need 64 x k contraction channels"), PIS_ERR_ARG;
-  if (format == 2) launch_wino4_filter(a, N, C, nullptr, 0, reinterpret_cast<__bf16*>(out), s, wino_gemm_out_h3());
+  if (format == 2) launch_wino4_filter(a, N, C, nullptr, 0, reinterpret_cast<__bf16*>(out), s, v.fused_h3);
   else  // format 1 of an input gradient: the batched GEMM, so U' with key 51 (ALGO_WINO4_DGRAD_T)
-    launch_wino4_filter(a, N, C, reinterpret_cast<float*>(out), 0, nullptr, s, false,
-                        dgrad && tune_get(PIS_TUNE_WINO_DGRAD_T) != 0);
+    launch_wino4_filter(a, N, C, reinterpret_cast<float*>(out), 0, nullptr, s, false, dgrad && v.dgrad_t);
   return launch_status("wino_filter");
 }
 
 // jobs: (w, out, contraction C, outputs N, dgrad, format) — validated by the caller
 int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, const int* C, const int* N,
-                              const int* dgrad, const int* format, hipStream_t s) {
+                              const int* dgrad, const int* format, hipStream_t s, const WinoVariants& v) {
   if (n <= 0) return PIS_OK;
   if (n > FILTER_MAX_JOBS) return set_error("pis_conv3x3_filters: more than 40 jobs"), PIS_ERR_ARG;
   FilterBatch fb{};
@@ -2861,11 +2766,11 @@ int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, co
   for (int k = 0; k < n; ++k) {
     if (dgrad[k] && (N[k] % 32 || C[k] % 32))
       return set_error("pis_conv3x3_filters: an input-gradient transform needs 32-aligned channels"), PIS_ERR_ARG;
-    const int planes = format[k] == 2 ? (wino_gemm_out_h3() ? 2 : 1) : 0;
+    const int planes = format[k] == 2 ? (v.fused_h3 ? 2 : 1) : 0;
     if (planes == 2 && (C[k] % 64 || N[k] % 4))
       return set_error("pis_conv3x3_filters: fp16x3 planes need 64 x k contraction channels"), PIS_ERR_ARG;
     const int blocks = planes == 2 ? N[k] / 4 : dgrad[k] ? (N[k] / 32) * (C[k] / 32) : grid_of((int64_t)N[k] * C[k]);
-    const int gt = dgrad[k] && format[k] == 1 && tune_get(PIS_TUNE_WINO_DGRAD_T) != 0;
+    const int gt = dgrad[k] && format[k] == 1 && v.dgrad_t;
     fb.j[k] = FilterJobDev{w[k], out[k], N[k], C[k], dgrad[k], planes, blocks, format[k] == 4 ? 6 : 4, gt};
     fb.start[k] = total;
     total += blocks;
@@ -2875,17 +2780,16 @@ int launch_wino4_filter_batch(int n, const float* const* w, void* const* out, co
   return launch_status("wino_filter_batch");
 }
 
-int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float* V, hipStream_t s, int m) {
+int launch_wino_input(const float* x, int ldx, int B, int H, int W, int C, float* V, hipStream_t s, int m,
+                      const WinoVariants& v) {
   const int64_t T = (int64_t)B * (H / m) * (W / m);
   if (m == 4)
-    launch_wino4_input(T, C, s, x, ldx, B, H, W, C, V);
+    launch_wino4_input(T, C, s, x, ldx, B, H, W, V, v);
   else
     hipLaunchKernelGGL(wino_input_kernel, dim3(grid_of(T * (C / 4))), dim3(256), 0, s, x, ldx, B, H, W, C, V);
   return launch_status("wino_input");
 }
 
-// channels per thread of the F(3x3,4x4) dz passes (pis_tune key 40): 2 where 256 is a multiple of
-// N / 2 (the bias partials' channel-group rule), else 4
 // channels per thread of the dz passes: 2 where 256 % (N / 2) == 0 (144-162 registers; the float4
 // form, needed for N = 1024, holds 256 + 30 and one wave per SIMD; measured neutral on the step)
 static int dz_vw(int N) { return N % 2 == 0 && 256 % (N / 2) == 0 ? 2 : 4; }
@@ -2900,41 +2804,32 @@ int wino_dz_blocks_max(int B, int H, int W, int N, int m) {
 }
 
 int launch_wino_dz(const float* dz, int ldz, int B, int H, int W, int N, float* E, hipStream_t s, int m,
-                   float* bpart) {
+                   const WinoVariants& v, float* bpart) {
   const int64_t T = (int64_t)B * (H / m) * (W / m);
-  if (m == 4 && wino_xform(XF_DZ2) && dz_vw(N) == 2)
-    hipLaunchKernelGGL(wino4_dz_cols_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, dz, ldz, B, H, W, N, E,
+  if (m == 4) {
+    // [single-load-phase form][4 channels per thread]
+    static void (*const fn[2][2])(const float*, int, int, int, int, int, float*, float*) = {
+        {wino4_dz_kernel<2>, wino4_dz_kernel<4>}, {wino4_dz_cols_kernel<2>, wino4_dz_cols_kernel<4>}};
+    const int vw = dz_vw(N);
+    hipLaunchKernelGGL(fn[v.dz_cols][vw == 4], dim3(grid_of(T * (N / vw))), dim3(256), 0, s, dz, ldz, B, H, W, N, E,
                        bpart);
-  else if (m == 4 && wino_xform(XF_DZ2))
-    hipLaunchKernelGGL(wino4_dz_cols_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, dz, ldz, B, H, W, N, E,
-                       bpart);
-  else if (m == 4 && dz_vw(N) == 2)
-    hipLaunchKernelGGL(wino4_dz_kernel<2>, dim3(grid_of(T * (N / 2))), dim3(256), 0, s, dz, ldz, B, H, W, N, E, bpart);
-  else if (m == 4)
-    hipLaunchKernelGGL(wino4_dz_kernel<4>, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, dz, ldz, B, H, W, N, E, bpart);
-  else
+  } else {
     hipLaunchKernelGGL(wino_dz_kernel, dim3(grid_of(T * (N / 4))), dim3(256), 0, s, dz, ldz, B, H, W, N, E);
+  }
   return launch_status("wino_dz");
 }
 
 int launch_wino_dz2(const float* dz, int ldz, int B, int H, int W, int N, float* V, float* E, float* bpart,
-                    hipStream_t s, float* tmax) {
+                    hipStream_t s, const WinoVariants& v, float* tmax) {
   const int64_t T = (int64_t)B * (H / 4) * (W / 4);
+  // [single-load-phase form][tile maxima][4 channels per thread]
+  static void (*const fn[2][2][2])(const float*, int, int, int, int, int, float*, float*, float*, float*) = {
+      {{wino4_dz2_kernel<false, 2>, wino4_dz2_kernel<false, 4>}, {wino4_dz2_kernel<true, 2>, wino4_dz2_kernel<true, 4>}},
+      {{wino4_dz2_cols_kernel<false, 2>, wino4_dz2_cols_kernel<false, 4>},
+       {wino4_dz2_cols_kernel<true, 2>, wino4_dz2_cols_kernel<true, 4>}}};
   const int vw = dz_vw(N);
-  const dim3 grid(grid_of(T * (N / vw)));
-  const bool cols = wino_xform(XF_DZ2);
-#define PIS_DZ2_LAUNCH(TM, VW)                                                                                     \
-  do {                                                                                                             \
-    if (cols) hipLaunchKernelGGL((wino4_dz2_cols_kernel<TM, VW>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, \
-                                 bpart, tmax);                                                                     \
-    else hipLaunchKernelGGL((wino4_dz2_kernel<TM, VW>), grid, dim3(256), 0, s, dz, ldz, B, H, W, N, V, E, bpart,   \
-                            tmax);                                                                                 \
-  } while (0)
-  if (tmax && vw == 2) PIS_DZ2_LAUNCH(true, 2);
-  else if (tmax) PIS_DZ2_LAUNCH(true, 4);
-  else if (vw == 2) PIS_DZ2_LAUNCH(false, 2);
-  else PIS_DZ2_LAUNCH(false, 4);
-#undef PIS_DZ2_LAUNCH
+  hipLaunchKernelGGL(fn[v.dz_cols][tmax != nullptr][vw == 4], dim3(grid_of(T * (N / vw))), dim3(256), 0, s, dz, ldz, B,
+                     H, W, N, V, E, bpart, tmax);
   return launch_status("wino_dz2");
 }
 
@@ -2961,7 +2856,8 @@ void wino_prep_record(const void* ws, int B, int H, int W, int C, int N, bool tm
 }
 
 // algo: what this call resolved to; the fused contraction reads tile maxima in fp16x3 (key 22)
-static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, const float** e) {
+static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, ConvAlgo algo, bool fused_h3,
+                           const float** e) {
   for (const auto& r : g_prep)
     if (r.ws == ws && r.B == B && r.H == H && r.W == W && r.C == C && r.N == N) {
       if ((r.e != nullptr) != (algo == ALGO_WINO4_DGRAD_T))
@@ -2970,7 +2866,7 @@ static int wino_prep_check(const void* ws, int B, int H, int W, int C, int N, Co
                          r.e ? "E alone" : "V(dz)", r.e ? "V(dz)" : "E"),
                PIS_ERR_ARG;
       *e = r.e;
-      if (r.tmax != (algo == ALGO_WINO4_FUSED && wino_gemm_out_h3()))
+      if (r.tmax != (algo == ALGO_WINO4_FUSED && fused_h3))
         return set_error("PIS_WINO_PREPARED: pis_conv3x3_bwd_prep wrote %s tile maxima but this call's kernel "
                          "choice needs %s (a pis_tune knob changed in between)",
                          r.tmax ? "" : "no", r.tmax ? "none" : "them"),
@@ -2987,26 +2883,20 @@ float* wino_tmax_slot(void* ws, int B, int H, int W, int C, int N) {
 }
 
 int launch_wino_wgrad_out(const float* M, int N, int C, float* dw, int accumulate, hipStream_t s, int m,
-                          int nsplit, int64_t sstride, WgradOutBias bias) {
+                          const WinoVariants& v, int nsplit, int64_t sstride, WgradOutBias bias) {
   if (bias.rows > 0 && !(m == 4 && ((int64_t)N * C) % 64 == 0))
     return set_error("wino_wgrad_out: the folded bias needs the tiled F(3x3,4x4) transform"), PIS_ERR_ARG;
   const int64_t NC = (int64_t)N * C;
   auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  if (m == 4 && NC % 64 == 0 && C % 4 == 0 && tune_get(PIS_TUNE_WGRAD_OUT) == 1 && a16(M) && a16(dw) &&
-      sstride % 4 == 0) {
+  if (m == 4 && NC % 64 == 0 && C % 4 == 0 && v.wgrad_out_v4 && a16(M) && a16(dw) && sstride % 4 == 0) {
     // the widest block that still leaves >= 512 blocks (every CU busy twice)
     const int nb = bias.rows > 0 ? (N + 255) / 256 : 0;
     const int epb = (NC % 256 == 0 && NC / 256 >= 512) ? 256 : (NC % 128 == 0 && NC / 128 >= 512) ? 128 : 64;
     const dim3 grid((unsigned)(NC / epb + nb));
-    if (epb == 256)
-      hipLaunchKernelGGL(wino4_wgrad_out_v4_kernel<256>, grid, dim3(256), 0, s, M, N, C, dw, accumulate, nsplit,
-                         sstride, bias, nb);
-    else if (epb == 128)
-      hipLaunchKernelGGL(wino4_wgrad_out_v4_kernel<128>, grid, dim3(256), 0, s, M, N, C, dw, accumulate, nsplit,
-                         sstride, bias, nb);
-    else
-      hipLaunchKernelGGL(wino4_wgrad_out_v4_kernel<64>, grid, dim3(256), 0, s, M, N, C, dw, accumulate, nsplit,
-                         sstride, bias, nb);
+    const auto fn = epb == 256   ? wino4_wgrad_out_v4_kernel<256>
+                    : epb == 128 ? wino4_wgrad_out_v4_kernel<128>
+                                 : wino4_wgrad_out_v4_kernel<64>;
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, s, M, N, C, dw, accumulate, nsplit, sstride, bias, nb);
   } else if (m == 4 && ((int64_t)N * C) % 64 == 0) {
     const int nb = bias.rows > 0 ? (N + 255) / 256 : 0;
     hipLaunchKernelGGL(wino4_wgrad_out_tiled_kernel, dim3((unsigned)((int64_t)N * C / 64 + nb)), dim3(256), 0, s, M,
@@ -3039,18 +2929,21 @@ extern "C" int pis_debug_gemm_nt(const float* A, const float* B, float* C, int M
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((int)cdiv(M, 128) * (N / bn), batch);
   const int64_t sa = (int64_t)M * K, sb = (int64_t)N * K, sc = (int64_t)M * N;
+  // the Winograd pipelines' own instantiations go through their launcher
+  const auto wino = [&](WinoGemm g) { return launch_wino_gemm(g, A, B, C, M, N, K, batch, s, "debug_gemm_nt"); };
   switch (variant) {
-    case 0: hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 128>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
+    case 0: return wino(WinoGemm::X6_128);
+    case 3: return wino(WinoGemm::F32_128);
+    case 4: return wino(WinoGemm::X6_64);
+    case 6: return wino(WinoGemm::X6_BK32_128);
+    case 7: return wino(WinoGemm::X6_BK32_64);
+    case 11: return wino(WinoGemm::H3_128);
+    case 12: return wino(WinoGemm::H3_64);
+    // the timing twins, the OCC-2 form and the unscaled fp16x3 form
     case 1: hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 128, 1>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     case 2: hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 128, 2>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 3: hipLaunchKernelGGL((gemm_nt_kernel<128, 128>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 4: hipLaunchKernelGGL((gemm_nt_x6_kernel<128, 64>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     case 5: hipLaunchKernelGGL((gemm_nt_x6_bk32_kernel<128, 128>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 6: hipLaunchKernelGGL((gemm_nt_x6_bk32_kernel<128, 128, 3>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 7: hipLaunchKernelGGL((gemm_nt_x6_bk32_kernel<128, 64, 3>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     case 10: hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3, false>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 11: hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
-    case 12: hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 64, 4>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     case 13: hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3, true, 1>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     case 14: hipLaunchKernelGGL((gemm_nt_h3_bk32_kernel<128, 128, 3, true, 2>), grid, dim3(256), 0, s, A, B, C, M, N, K, sa, sb, sc); break;
     default: set_error("pis_debug_gemm_nt: unknown variant %d", variant); return PIS_ERR_ARG;

@@ -42,6 +42,23 @@ CASES = {
     "f6": (24, 24, 256, 256, {47: 1}, {}, (4, 4), ("wino_gemm", "wino_wgrad_gemm")),
 }
 
+# The Winograd launch variants (csrc/conv3x3_plan.h WinoGemm, WinoVariants, wino_fused_form), one key off its
+# default per case, recorded from the launch ladders that csrc/winograd.hip held before the planner named them.
+BATCHED, FUSED = (16, 16, 128, 256), (32, 64, 64, 64)  # 16 tiles; 128 tiles = 4 groups of 32
+for _key, _values in ((10, (0, 1, 2, 3)), (17, (4,)), (46, (0,)), (48, (0,)), (50, (0, 2, 4)), (51, (0, 2))):
+    for _v in _values:  # the batched GEMM's arithmetic; transform widths and forms; the overlap-add input gradient
+        CASES[f"batched_f4_k{_key}_{_v}"] = (*BATCHED, {_key: _v}, {}, (1, 1), ("wino_gemm",))
+CASES["f2_k11_0"] = (16, 16, 256, 256, {11: 0}, {}, (0, 0), ("wino_gemm",))
+for _key, _values in ((15, (2, 3, 4)), (22, (0,)), (25, (0,)), (17, (4,))):
+    for _v in _values:  # groups per block, bf16x6 planes, lockstep waves, 4-channel transforms
+        CASES[f"fused_f4_k{_key}_{_v}"] = (*FUSED, {_key: _v}, {}, (2, 2), ("wino_gemm_out",))
+CASES["fused_f4_8groups_k15_4"] = (64, 64, 64, 64, {15: 4}, {}, (2, 2), ("wino_gemm_out",))
+# the 128-channel fused form needs T >= 2 C tiles
+CASES["fused_f4_c128"] = (64, 64, 128, 128, {}, {}, (2, 2), ("wino_gemm_out",))
+CASES["fused_f4_c128_k22_0"] = (64, 64, 128, 128, {22: 0}, {}, (2, 2), ("wino_gemm_out",))
+CASES["f6_k47_2"] = (24, 24, 256, 256, {47: 2}, {}, (4, 4), ("wino_gemm",))
+CASES["f6_k47_3"] = (24, 24, 256, 256, {47: 3}, {}, (4, 4), ("wino_gemm",))
+
 
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
